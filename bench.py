@@ -516,6 +516,52 @@ def stand_in_runs(spasm_amd, workloads):
 
 
 # --------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 42013
+
+
+def dump_outputs(torch, spasm_amd, W, st, nrows, m, stream, out_dir):
+    """what the last timed step computed, as a caller of spasm_hip_dschur receives it (spasm_hip_dschur_fetch: row pointers,
+    column indices and balanced values of S, rows in the order of the row list), written as out_dir/<name>.npy: the row pointers
+    of every row, and every entry of a fixed sample of rows drawn with a fixed seed (S of mk13.b5 holds 5e8 entries), under
+    DUMP_LIMIT_BYTES in all.  Returns {file name: bytes}."""
+    dev = torch.device("cuda", torch.cuda.current_device())
+    Sp = torch.empty(nrows + 1, dtype=torch.int64, device=dev)
+    Sj = torch.empty(max(st.nnz, 1), dtype=torch.int32, device=dev)
+    Sx = torch.empty(max(st.nnz, 1), dtype=torch.int32, device=dev)
+    spasm_amd.lib().spasm_hip_dschur_fetch(W._h, Sp.data_ptr(), Sj.data_ptr(), Sx.data_ptr(), stream.cuda_stream)
+    torch.cuda.synchronize()
+    p = Sp.cpu().numpy()
+    if int(p[-1]) != st.nnz:
+        raise SystemExit("bench.py: the fetched Schur complement holds %d entries, the step reported %d" % (int(p[-1]), st.nnz))
+    # the sample: the first k rows of a seeded permutation (k halved until their entries fit), in the order of the row list
+    order = np.random.default_rng(DUMP_SAMPLE_SEED).permutation(nrows)
+    k = min(nrows, 4096)
+    budget = DUMP_LIMIT_BYTES - 8 * (nrows + 1) - 16 * (k + 1) - 4096
+    while k > 1 and 8 * int(np.sum(p[order[:k] + 1] - p[order[:k]])) > budget:
+        k //= 2
+    sample = np.sort(order[:k])
+    lengths = p[sample + 1] - p[sample]
+    idx = np.concatenate([np.arange(p[r], p[r + 1], dtype=np.int64) for r in sample] + [np.zeros(0, np.int64)])
+    sel = torch.from_numpy(idx).to(dev)
+    col_type = np.float32 if m < (1 << 24) else np.float64          # (exact: integers below 2^24; values are balanced mod 42013)
+    arrays = {"S_row_pointers": p.astype(np.float64),
+              "S_sample_rows": sample.astype(np.float64),
+              "S_sample_row_pointers": np.concatenate([[0], np.cumsum(lengths)]).astype(np.float64),
+              "S_sample_columns": Sj.index_select(0, sel).cpu().numpy().astype(col_type),
+              "S_sample_values": Sx.index_select(0, sel).cpu().numpy().astype(np.float32)}
+    del Sp, Sj, Sx, sel
+    torch.cuda.empty_cache()
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        written[name + ".npy"] = os.path.getsize(path)
+    assert sum(written.values()) <= DUMP_LIMIT_BYTES, written
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -535,7 +581,14 @@ def main():
                          "about a minute more, 40 GB of device memory) and report it as `beyond_scale`")
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the row-by-row comparison, the dense-tail probe and the end-to-end runs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the Schur complement: all row pointers, the entries "
+                         "of a fixed seeded sample of rows) as DIR/<name>.npy, float32/float64, at most 64 MB in all; one process only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("SPASM_BENCH_FORCE_DIST") == "1"):
+        ap.error("--dump-outputs: one process on one GPU only")
 
     import torch
     import spasm_amd
@@ -759,6 +812,10 @@ def main():
             step()
         elapsed, (_, ms_sum, bytes_of, st) = timed(lambda: run_steps(args.steps))
         kernel_steps = args.steps
+    dumped = None
+    if args.dump_outputs:
+        # (before anything else runs through the workspace: it holds the last timed step's S)
+        dumped = dump_outputs(torch, spasm_amd, W, st, len(my_rows), A.m, stream, args.dump_outputs)
 
     total_nnz_all = int(st.nnz)
     if use_dist and split == "columns":
@@ -854,6 +911,8 @@ def main():
                                  "median of 3 builds after a first one that is not counted (it loads the code object and fills the buffer cache)",
             "rows_per_s_cold": total_rows / (elapsed / args.steps + 1e-3 * statistics.median(image_ms)),
         }
+        if dumped is not None:
+            out["outputs_dumped"] = {"dir": args.dump_outputs, "files": dumped}
         if slab_only is not None:
             out["dist_product_path"] = {"what": "value / ms_per_step: spasm_hip_schur_resident = spasm_hip_schur as the driver calls it, communicator installed "
                                                 "(slab or slice, all-gatherv of S, stitching); roofline.kernels: measured in the slab_only steps",

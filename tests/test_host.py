@@ -6,7 +6,7 @@ import re
 import numpy as np
 import pytest
 
-from conftest import ALL_TEST_MATRICES, ROOT, matrix_path
+from conftest import ALL_TEST_MATRICES, ROOT, csr_arrays, csr_of, matrix_path, reference_vectors
 
 import spasm_amd
 from spasm_amd.matrix import view_csr
@@ -435,10 +435,9 @@ def test_matrix_market_files_load_like_the_reference(oracle, name, p, tmp_path):
     assert np.array_equal(A.p, B.p) and np.array_equal(A.j, B.j) and np.array_equal(A.x, B.x)
     T = spasm_amd.load(path, p, transpose_if_wide=True)
     assert T.n >= T.m
-    if oracle.ref_available():
-        R = oracle.ref_load(path, p)
-        assert (R.n, R.m) == (B.n, B.m)
-        assert np.array_equal(R.p, B.p) and np.array_equal(R.j, B.j) and np.array_equal(R.x, B.x)
+    R = csr_of(oracle, reference_vectors(oracle, "mtx_load", "%s|%d" % (name, p), lambda: csr_arrays(oracle.ref_load(path, p))), p)
+    assert (R.n, R.m) == (B.n, B.m)
+    assert np.array_equal(R.p, B.p) and np.array_equal(R.j, B.j) and np.array_equal(R.x, B.x)
 
 
 def test_matrix_market_header_is_validated(tmp_path):

@@ -3,7 +3,8 @@
 Two anchors (see oracle/spasm_oracle.h):
   * the real reference compiled into oracle/_ref/libspasm_ref.so -- exact
     equality, entry order included, on the reference's own test matrices and
-    moduli (skipped only where that library could not be built);
+    moduli; where that library could not be built, against what it returned
+    on the same inputs, stored under tests/golden/reference/;
   * the properties the reference's tests assert (tests/GFp.c, tests/schur.c,
     tests/schur_dense.c, tests/echelonize.c, tests/dense_rref_ffpack.c) and an
     independent numpy elimination for ranks.
@@ -11,7 +12,7 @@ Two anchors (see oracle/spasm_oracle.h):
 import numpy as np
 import pytest
 
-from conftest import ALL_MODULI, ALL_TEST_MATRICES, matrix_path
+from conftest import ALL_MODULI, ALL_TEST_MATRICES, csr_arrays, csr_of, matrix_path, reference_vectors
 
 SMALL_SET = [m for m in ALL_TEST_MATRICES if m not in ("mat364.sms", "trefethen_500.sms", "medium.sms", "m1.sms")]
 
@@ -58,21 +59,31 @@ def test_field_inverse_all(oracle, p):
 
 @pytest.mark.parametrize("p", ALL_MODULI + [0x7fffffff, 3037000493])
 def test_field_matches_reference(oracle, p):
-    need_ref(oracle)
-    L, R = oracle.lib(), oracle.ref()
-    F = oracle.ref_field(p)
-    import ctypes as C
-    rng = np.random.default_rng(p % 1000)
-    vals = rng.integers(-(p // 2), p // 2 + 1, size=(2000, 3))
-    for a, b, c in vals.tolist():
-        assert L.orc_zp_add(p, a, b) == R.spasm_ZZp_add(C.byref(F), a, b)
-        assert L.orc_zp_sub(p, a, b) == R.spasm_ZZp_sub(C.byref(F), a, b)
-        assert L.orc_zp_mul(p, a, b) == R.spasm_ZZp_mul(C.byref(F), a, b)
-        assert L.orc_zp_axpy(p, a, b, c) == R.spasm_ZZp_axpy(C.byref(F), a, b, c)
+    L = oracle.lib()
+
+    def live():
+        import ctypes as C
+        R = oracle.ref()
+        F = oracle.ref_field(p)
+        rng = np.random.default_rng(p % 1000)
+        vals = rng.integers(-(p // 2), p // 2 + 1, size=(2000, 3))
+        ops = [[R.spasm_ZZp_add(C.byref(F), a, b), R.spasm_ZZp_sub(C.byref(F), a, b), R.spasm_ZZp_mul(C.byref(F), a, b),
+                R.spasm_ZZp_axpy(C.byref(F), a, b, c), R.spasm_ZZp_inverse(C.byref(F), a) if a % p else 0]
+               for a, b, c in vals.tolist()]
+        big = rng.integers(-2**62, 2**62, size=200)
+        return {"vals": vals, "ops": np.array(ops, np.int64), "big": big,
+                "init": np.array([R.spasm_ZZp_init(C.byref(F), v) for v in big.tolist()], np.int64)}
+
+    want = reference_vectors(oracle, "field_%d" % p, "values", live)
+    for (a, b, c), (add, sub, mul, axpy, inv) in zip(want["vals"].tolist(), want["ops"].tolist()):
+        assert L.orc_zp_add(p, a, b) == add
+        assert L.orc_zp_sub(p, a, b) == sub
+        assert L.orc_zp_mul(p, a, b) == mul
+        assert L.orc_zp_axpy(p, a, b, c) == axpy
         if a % p:
-            assert L.orc_zp_inverse(p, a) == R.spasm_ZZp_inverse(C.byref(F), a)
-    for big in rng.integers(-2**62, 2**62, size=200).tolist():
-        assert L.orc_zp_init(p, big) == R.spasm_ZZp_init(C.byref(F), big)
+            assert L.orc_zp_inverse(p, a) == inv
+    for big, init in zip(want["big"].tolist(), want["init"].tolist()):
+        assert L.orc_zp_init(p, big) == init
 
 
 def test_prng_golden_is_reference(oracle):
@@ -93,11 +104,11 @@ def test_prng_golden_is_reference(oracle):
 # ---------------------------------------------------------------- compress
 @pytest.mark.parametrize("name", ALL_TEST_MATRICES)
 def test_compress_matches_reference(oracle, name):
-    need_ref(oracle)
     for p in (257, 4294967291):
         n, m, ti, tj, tx = oracle.read_sms(matrix_path(name))
         A = oracle.compress(p, n, m, ti, tj, tx)
-        B = oracle.ref_compress(p, n, m, ti, tj, tx)
+        B = csr_of(oracle, reference_vectors(oracle, "compress", "%s|%d" % (name, p),
+                                             lambda: csr_arrays(oracle.ref_compress(p, n, m, ti, tj, tx))), p)
         assert (A.n, A.m) == (B.n, B.m)
         assert np.array_equal(A.p, B.p) and np.array_equal(A.j, B.j) and np.array_equal(A.x, B.x)
 
@@ -114,35 +125,48 @@ def _round0(oracle, name, p, use_ref=False):
 @pytest.mark.parametrize("name", ALL_TEST_MATRICES)
 @pytest.mark.parametrize("p", [257, 189812507])
 def test_pivots_match_reference(oracle, name, p):
-    need_ref(oracle)
     A, npiv, perm, F = _round0(oracle, name, p)
-    _, npiv_r, perm_r, F_r = _round0(oracle, name, p, use_ref=True)
-    assert npiv == npiv_r
-    assert np.array_equal(perm, perm_r)
-    assert np.array_equal(F.qinv, F_r.qinv)
-    assert np.array_equal(F.U.p, F_r.U.p) and np.array_equal(F.U.j, F_r.U.j) and np.array_equal(F.U.x, F_r.U.x)
+
+    def live():
+        _, npiv_r, perm_r, F_r = _round0(oracle, name, p, use_ref=True)
+        return dict(csr_arrays(F_r.U), npiv=npiv_r, perm=perm_r, qinv=F_r.qinv)
+
+    want = reference_vectors(oracle, "pivots", "%s|%d" % (name, p), live)
+    assert npiv == int(want["npiv"])
+    assert np.array_equal(perm, want["perm"])
+    assert np.array_equal(F.qinv, want["qinv"])
+    assert np.array_equal(F.U.p, want["p"]) and np.array_equal(F.U.j, want["j"]) and np.array_equal(F.U.x, want["x"])
 
 
 @pytest.mark.parametrize("name", SMALL_SET)
 def test_triangular_solve_matches_reference(oracle, name):
-    need_ref(oracle)
     p = 65537
     A, npiv, perm, F = _round0(oracle, name, p)
+
+    def live(i):
+        pat_r, x_r = oracle.ref_solve_row(F.U, F.qinv, A, i)
+        return {"pat": pat_r, "values": x_r[pat_r]}
+
     for i in perm[npiv:npiv + 25]:
         pat, x = oracle.solve_row(F.U, F.qinv, A, int(i))
-        pat_r, x_r = oracle.ref_solve_row(F.U, F.qinv, A, int(i))
-        assert np.array_equal(pat, pat_r)
-        assert np.array_equal(x[pat], x_r[pat_r])
+        want = reference_vectors(oracle, "solve", "%s|%d" % (name, i), lambda: live(int(i)))
+        assert np.array_equal(pat, want["pat"])
+        assert np.array_equal(x[pat], want["values"])
 
 
 @pytest.mark.parametrize("name", ALL_TEST_MATRICES)
 @pytest.mark.parametrize("p", ALL_MODULI)
 def test_schur_matches_reference(oracle, name, p):
-    need_ref(oracle)
     A, npiv, perm, F = _round0(oracle, name, p)
     rows = perm[npiv:]
     S, p_out, _ = oracle.schur(A, rows, F)
-    S_r, p_out_r = oracle.ref_schur(A, rows, F, threads=1)
+
+    def live():
+        S_r, p_out_r = oracle.ref_schur(A, rows, F, threads=1)
+        return dict(csr_arrays(S_r), p_out=p_out_r)
+
+    want = reference_vectors(oracle, "schur_%d" % p, name, live)
+    S_r, p_out_r = csr_of(oracle, want, p), want["p_out"]
     assert np.array_equal(p_out, p_out_r)
     assert np.array_equal(S.p, S_r.p) and np.array_equal(S.j, S_r.j) and np.array_equal(S.x, S_r.x)
     # property of tests/schur.c:62-72: nothing is left under a pivot
@@ -152,12 +176,25 @@ def test_schur_matches_reference(oracle, name, p):
 @pytest.mark.parametrize("name", SMALL_SET)
 def test_schur_multithreaded_reference_same_matrix(oracle, name):
     """with several OpenMP threads the reference permutes rows; as a set of rows it is the same."""
-    need_ref(oracle)
     p = 42013
     A, npiv, perm, F = _round0(oracle, name, p)
     rows = perm[npiv:]
     S, p_out, _ = oracle.schur(A, rows, F)
-    S_r, p_out_r = oracle.ref_schur(A, rows, F, threads=4)
+
+    def live():
+        # (stored, and compared with what is stored, in the order of the rows of A: the threads' order changes from run to run)
+        S_r, p_out_r = oracle.ref_schur(A, rows, F, threads=4)
+        order = np.argsort(p_out_r, kind="stable")
+        canon = S_r.canonical()
+        lengths = np.array([len(canon[t][0]) for t in order], np.int64)
+        return {"n": S_r.n, "m": S_r.m, "p": np.concatenate([[0], np.cumsum(lengths)]),
+                "j": np.concatenate([canon[t][0] for t in order] + [np.zeros(0, np.int64)]),
+                "x": np.concatenate([canon[t][1] for t in order] + [np.zeros(0, np.int64)]),
+                "p_out": p_out_r[order]}
+
+    want = reference_vectors(oracle, "schur_threads", "%s|%d" % (name, p), live)
+    S_r, p_out_r = csr_of(oracle, want, p), want["p_out"]
+    assert len(p_out_r) == len(p_out)
     mine = {int(r): c for r, c in zip(p_out, S.canonical())}
     for r, (jj, xx) in zip(p_out_r, S_r.canonical()):
         a, b = mine[int(r)]
@@ -167,11 +204,16 @@ def test_schur_multithreaded_reference_same_matrix(oracle, name):
 @pytest.mark.parametrize("name", SMALL_SET)
 @pytest.mark.parametrize("p", [257, 65537, 4294967291])
 def test_schur_dense_matches_reference(oracle, name, p):
-    need_ref(oracle)
     A, npiv, perm, F = _round0(oracle, name, p)
     rows = perm[npiv:]
     S, q, p_out = oracle.schur_dense(A, rows, F)
-    S_r, q_r, p_out_r = oracle.ref_schur_dense(A, rows, F)
+
+    def live():
+        S_r, q_r, p_out_r = oracle.ref_schur_dense(A, rows, F)
+        return {"S": S_r, "q": q_r, "p_out": p_out_r}
+
+    want = reference_vectors(oracle, "schur_dense", "%s|%d" % (name, p), live)
+    S_r, q_r, p_out_r = want["S"], want["q"], want["p_out"]
     assert np.array_equal(q, q_r) and np.array_equal(p_out, p_out_r)
     assert np.array_equal(S, S_r)
 
@@ -249,11 +291,16 @@ def test_echelonize_modes_agree(oracle, name):
 
 @pytest.mark.parametrize("name", SMALL_SET)
 def test_rref_matches_reference(oracle, name):
-    need_ref(oracle)
     p = 65537
     A = oracle.load_sms(matrix_path(name), p)
     F = oracle.echelonize(A)
     R, Rq = oracle.rref(F)
-    R_r, Rq_r = oracle.ref_rref(F)
+
+    def live():
+        R_r, Rq_r = oracle.ref_rref(F)
+        return dict(csr_arrays(R_r), q=Rq_r)
+
+    want = reference_vectors(oracle, "rref", name, live)
+    R_r, Rq_r = csr_of(oracle, want, p), want["q"]
     assert np.array_equal(Rq, Rq_r)
     assert oracle.same_matrix(R, R_r)
