@@ -237,6 +237,31 @@ int spasm_hip_echelonize_counters(long long *out, int count);
 struct spasm_csr *spasm_hip_rref(const struct spasm_lu *fact, int *Rqinv);
 struct spasm_csr *spasm_hip_kernel(const struct spasm_lu *fact);
 
+/* --- solving X.A = B over the factorization (replace spasm_solve.c:13, :52; spasm_amd/csrc/solve.hip) ---
+ * fact must come from an echelonization with opts->L = 1: fact->L (rows of A x rank) and fact->p (pivot j of L sits on row
+ * p[j]).  Three sweeps on the device, every right-hand side of a call at once: F (z.U = b on the pivot columns), C (is b in the
+ * row space of U?), B (y.L_piv = z); x[p[j]] = y_j.  X is bit-identical to the reference's, rows without a solution included
+ * (the reference returns its x for them too).  Violations die like the rest of the library: fact->L == NULL, a B whose width
+ * is not U->m or whose modulus is not the factorization's, a U whose pivots are not unit entries at the start of their rows,
+ * a row p[j] of L without an entry in column j. */
+bool spasm_hip_solve(const struct spasm_lu *fact, const spasm_ZZp *b, spasm_ZZp *x);                 /* spasm_solve.c:13 */
+/* B->n x L->n, entries of a row by increasing column; ok (may be NULL): ok[i] iff row i of B lies in the row space of U */
+struct spasm_csr *spasm_hip_gesv(const struct spasm_lu *fact, const struct spasm_csr *B, bool *ok);  /* spasm_solve.c:52 */
+
+/* A plan for repeated solves against one factorization (spasm_hip_gesv is create + solve + destroy): the dependency lists and
+ * level schedules of F and B on the host, then uploaded.  The plan copies what it needs: fact may be freed after create. */
+typedef struct spasm_hip_solver spasm_hip_solver;
+spasm_hip_solver *spasm_hip_solver_create(const struct spasm_lu *fact);
+struct spasm_csr *spasm_hip_solver_gesv(spasm_hip_solver *S, const struct spasm_csr *B, bool *ok);
+void spasm_hip_solver_destroy(spasm_hip_solver *S);
+/* out[0] levels of F, out[1] levels of B, out[2] / out[3] their launches per batch of right-hand sides (runs of thin levels
+ * share one launch) */
+void spasm_hip_solver_levels(const spasm_hip_solver *S, int *out);
+/* the plan and the last solve: [0] seconds of create, device ms of [1] the scatter of B, [2] F, [3] C, [4] B, [5] the emission
+ * of X; launches of [6] F, [7] B, [8] everything; [9] algorithmic bytes of the three sweeps; [10] batches, [11] right-hand
+ * sides per batch (sized against the free device memory).  Returns how many there are (16, the rest 0). */
+int spasm_hip_solver_stats(const spasm_hip_solver *S, double *out, int count);
+
 /* ======================================================================
  * (D) device-resident entry points
  * ====================================================================== */

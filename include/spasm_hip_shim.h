@@ -34,6 +34,10 @@
 #define spasm_kernel                  spasm_hip_kernel
 #define spasm_pivots_extract_structural spasm_hip_pivots_extract_structural
 
+/* solving X.A = B over the factorization (spasm_solve.c) */
+#define spasm_solve                   spasm_hip_solve
+#define spasm_gesv                    spasm_hip_gesv
+
 /* containers, field, I/O (spasm_util.c, spasm_ZZp.c, spasm_triplet.c, spasm_transpose.c, spasm_io.c) */
 #define spasm_malloc                  spasm_hip_malloc
 #define spasm_calloc                  spasm_hip_calloc

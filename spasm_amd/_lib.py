@@ -92,6 +92,13 @@ def lib():
         "spasm_hip_forget_cached_images": (None, []),
         "spasm_hip_allgatherv_plan": (ci, [ci, ci, C.POINTER(i64), vp, ci, C.POINTER(i64), C.POINTER(i64)]),
         "spasm_hip_column_slab": (ci, [pcsr, plu, ci, ci, C.POINTER(pcsr), C.POINTER(plu), pint]),
+        "spasm_hip_solve": (C.c_bool, [plu, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "spasm_hip_gesv": (pcsr, [plu, pcsr, C.POINTER(C.c_bool)]),
+        "spasm_hip_solver_create": (vp, [plu]),
+        "spasm_hip_solver_gesv": (pcsr, [vp, pcsr, C.POINTER(C.c_bool)]),
+        "spasm_hip_solver_destroy": (None, [vp]),
+        "spasm_hip_solver_levels": (None, [vp, pint]),
+        "spasm_hip_solver_stats": (ci, [vp, C.POINTER(C.c_double), ci]),
     }
     for name, (res, args) in sig.items():
         try:

@@ -3,8 +3,13 @@
  *
  * An unmodified object file of cbouilla/spasm (tools/rank.o, tools/kernel.o, ...) that is linked against this
  * library before the reference's libspasm gets spasm_echelonize, spasm_schur*, spasm_ffpack_*, spasm_rref and
- * spasm_kernel from the GPU; everything else (certificates, solvers, Dulmage-Mendelsohn, I/O) stays the
+ * spasm_kernel and spasm_gesv from the GPU; everything else (certificates, Dulmage-Mendelsohn, I/O, ...) stays the
  * reference's.  Signatures: src/spasm.h (cited per function in include/spasm_hip.h).
+ *
+ * spasm_solve is deliberately NOT exported: the reference's certificate code calls it from inside its own library
+ * (spasm_certificate.c:67,87), and this library is linked first, so exporting it would reroute those calls -- the programs
+ * linked this way today (tools/rank.c --certificate among them) must keep doing exactly what they did.  A program that wants
+ * the single right-hand side on the GPU goes through the shim (spasm_hip_shim.h) or calls spasm_hip_solve.
  */
 #include "../../include/spasm_hip.h"
 
@@ -52,3 +57,5 @@ const char *spasm_datatype_name(spasm_datatype datatype) { return spasm_hip_data
 
 struct spasm_csr *spasm_rref(const struct spasm_lu *fact, int *Rqinv) { return spasm_hip_rref(fact, Rqinv); }
 struct spasm_csr *spasm_kernel(const struct spasm_lu *fact) { return spasm_hip_kernel(fact); }
+
+struct spasm_csr *spasm_gesv(const struct spasm_lu *fact, const struct spasm_csr *B, bool *ok) { return spasm_hip_gesv(fact, B, ok); }

@@ -82,6 +82,11 @@ def _lu_for(F, extra_rows, extra_nz):
     lu.qinv = _ip(qinv)
     lu.p = None
     lu.Ltmp = None
+    if getattr(F, "L", None) is not None and getattr(F, "Lp", None) is not None:
+        # L and p of an echelonization with opts.L: views of F's arrays, kept alive by lu
+        lu._keep = (F.L, view_csr(F.L), np.ascontiguousarray(F.Lp, np.int32))
+        lu.L = C.pointer(lu._keep[1])
+        lu.p = _ip(lu._keep[2])
     return lu, up, qinv
 
 
@@ -264,3 +269,107 @@ def kernel(F):
     L.spasm_hip_csr_free(k)
     L.spasm_hip_csr_free(up)
     return K
+
+
+def _check_solvable(F, m, prime, what):
+    if getattr(F, "L", None) is None or getattr(F, "Lp", None) is None:
+        raise ValueError("spasm_amd.%s needs a factorization with L (echelonize with opts.L = True)" % what)
+    if F.L.m != F.U.n or len(F.Lp) < F.U.n:
+        raise ValueError("spasm_amd.%s: L has %d columns and %d pivot rows, U has %d rows" % (what, F.L.m, len(F.Lp), F.U.n))
+    if F.L.prime != F.U.prime:
+        raise ValueError("spasm_amd.%s: L is mod %d, U mod %d" % (what, F.L.prime, F.U.prime))
+    if m != F.U.m:
+        raise ValueError("spasm_amd.%s: the right-hand sides have %d columns, U has %d" % (what, m, F.U.m))
+    if prime != F.U.prime:
+        raise ValueError("spasm_amd.%s: the right-hand sides are mod %d, the factorization mod %d" % (what, prime, F.U.prime))
+
+
+def _gesv_call(fn, B):
+    b = view_csr(B)
+    ok = np.zeros(max(B.n, 1), np.bool_)
+    x = fn(C.byref(b), ok.ctypes.data_as(C.POINTER(C.c_bool)))
+    X = copy_csr(x)
+    lib().spasm_hip_csr_free(x)
+    return X, ok[:B.n].copy()
+
+
+class Solver:
+    """spasm_hip_solver: the plan of the three sweeps for one factorization (with L), reused by every gesv() call.
+    levels: dict(forward, back, forward_launches, back_launches)."""
+
+    def __init__(self, F):
+        _check_solvable(F, F.U.m, F.U.prime, "Solver")
+        require_gpu("Solver")
+        L = lib()
+        lu, up, qinv = _lu_for(F, 0, 0)
+        self._S = L.spasm_hip_solver_create(C.byref(lu))
+        L.spasm_hip_csr_free(up)
+        self.m, self.n, self.prime = F.U.m, F.L.n, F.U.prime
+        out = (C.c_int * 4)()
+        L.spasm_hip_solver_levels(self._S, out)
+        self.levels = {"forward": out[0], "back": out[1], "forward_launches": out[2], "back_launches": out[3]}
+
+    def gesv(self, B):
+        """(X, ok) as spasm_gesv (spasm_solve.c:52) returns them: X is B.n x (rows of A), ok[i] iff row i of B lies in the row
+        space of U; rows without a solution hold what the reference computes for them."""
+        if self._S is None:
+            raise ValueError("Solver is closed")
+        if B.m != self.m or B.prime != self.prime:
+            raise ValueError("spasm_amd.Solver.gesv: B is %d columns mod %d, the factorization %d columns mod %d"
+                             % (B.m, B.prime, self.m, self.prime))
+        S = self._S
+        return _gesv_call(lambda b, ok: lib().spasm_hip_solver_gesv(S, b, ok), B)
+
+    def stats(self):
+        """spasm_hip_solver_stats: the plan's seconds and the last gesv's device ms per sweep, launches, bytes, batches."""
+        out = (C.c_double * 16)()
+        lib().spasm_hip_solver_stats(self._S, out, 16)
+        keys = ("plan_s", "scatter_ms", "forward_ms", "check_ms", "back_ms", "emit_ms", "forward_launches", "back_launches",
+                "launches", "sweep_bytes", "batches", "rhs_per_batch")
+        return {k: out[t] for t, k in enumerate(keys)}
+
+    def close(self):
+        if self._S is not None:
+            lib().spasm_hip_solver_destroy(self._S)
+            self._S = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def gesv(F, B):
+    """spasm_gesv (spasm_solve.c:52): solves X.A = B over F (from echelonize with opts.L).  Returns (X: Csr, ok: bool array)."""
+    _check_solvable(F, B.m, B.prime, "gesv")
+    require_gpu("gesv")
+    L = lib()
+    lu, up, qinv = _lu_for(F, 0, 0)
+    try:
+        return _gesv_call(lambda b, ok: L.spasm_hip_gesv(C.byref(lu), b, ok), B)
+    finally:
+        L.spasm_hip_csr_free(up)
+
+
+def solve(F, b):
+    """spasm_solve (spasm_solve.c:13): x.A = b for one dense b (U.m values).  Returns (x: int32 array of A's rows, ok)."""
+    b = np.ascontiguousarray(b, np.int32)
+    if b.ndim != 1:
+        raise ValueError("spasm_amd.solve: b must be one vector")
+    _check_solvable(F, len(b), F.U.prime, "solve")
+    require_gpu("solve")
+    L = lib()
+    lu, up, qinv = _lu_for(F, 0, 0)
+    x = np.zeros(max(F.L.n, 1), np.int32)
+    try:
+        ok = L.spasm_hip_solve(C.byref(lu), b.ctypes.data_as(C.POINTER(C.c_int32)), x.ctypes.data_as(C.POINTER(C.c_int32)))
+    finally:
+        L.spasm_hip_csr_free(up)
+    return x[:F.L.n], bool(ok)

@@ -27,11 +27,14 @@ class Csr:
 
 
 class Fact:
-    """the part of struct spasm_lu the path uses: U (pivot first, unit) and qinv."""
+    """the part of struct spasm_lu the path uses: U (pivot first, unit) and qinv; with opts.L, echelonize() also attaches
+    L (a Csr, rows of A x rank) and Lp (pivot j of L sits on row Lp[j]), which gesv / solve need."""
 
-    def __init__(self, U, qinv):
+    def __init__(self, U, qinv, L=None, Lp=None):
         self.U = U
         self.qinv = np.ascontiguousarray(qinv, dtype=np.int32)
+        self.L = L
+        self.Lp = None if Lp is None else np.ascontiguousarray(Lp, dtype=np.int32)
 
     @property
     def r(self):
