@@ -118,6 +118,16 @@ struct echelonize_opts {               /* spasm.h:84-108 */
 	double low_rank_start_weight;
 };
 
+struct spasm_rank_certificate {        /* spasm.h:110-118 */
+	int r;
+	i64 prime;
+	u8 hash[32];
+	int *i;                            /* size r */
+	int *j;                            /* size r */
+	spasm_ZZp *x;                      /* size r */
+	spasm_ZZp *y;                      /* size r */
+};
+
 typedef enum {SPASM_DOUBLE, SPASM_FLOAT, SPASM_I64} spasm_datatype;   /* spasm.h:139 */
 #endif /* _SPASM_H */
 
@@ -261,6 +271,38 @@ void spasm_hip_solver_levels(const spasm_hip_solver *S, int *out);
  * of X; launches of [6] F, [7] B, [8] everything; [9] algorithmic bytes of the three sweeps; [10] batches, [11] right-hand
  * sides per batch (sized against the free device memory).  Returns how many there are (16, the rest 0). */
 int spasm_hip_solver_stats(const spasm_hip_solver *S, double *out, int count);
+
+/* --- products x.A and rank certificates (replace spasm_spmv.c:9-21, spasm_certificate.c:21-270; spasm_amd/csrc/spmv.hip,
+ * host_cert.cpp) ---
+ * x.A runs on the device: a column-major image of A is built there (count, scan, fill), then every entry of the result is
+ * written once by one lane or one wave, all k vectors in one pass over A.  A goes up once per call.  Any odd modulus. */
+/* Y (k x A->m, row-major) += X (k x A->n, row-major) . A, 0 <= k; values of X and Y may be any representatives, Y comes back
+ * balanced */
+void spasm_hip_xApy_batch(const struct spasm_csr *A, int k, const spasm_ZZp *X, spasm_ZZp *Y);
+void spasm_hip_xApy(const spasm_ZZp *x, const struct spasm_csr *A, spasm_ZZp *y);                  /* spasm_spmv.c:9 */
+/* the last x.A call: device ms of [0] the upload of A, [1] building its column-major image, [2] the product; [3] its algorithmic
+ * bytes, [4] k, [5] short / [6] long columns, [7] entries of A.  Returns how many there are (8). */
+int spasm_hip_xApy_stats(double *out, int count);
+
+/* Eberly's rank certificate, bit-identical to the reference's on the same factorization (fact from an echelonization with
+ * opts->L = 1; both right-hand sides go through one spasm_hip_gesv call).  Dies on fact->L == NULL or a modulus mismatch.
+ * The result is malloc'ed; spasm_hip_rank_certificate_free releases it. */
+struct spasm_rank_certificate *spasm_hip_certificate_rank_create(const struct spasm_csr *A, const u8 *hash,
+                                                                 const struct spasm_lu *fact);          /* spasm_certificate.c:21 */
+/* the reference's checks in its order (hash, prime, index ranges, then x.A = alpha on j and y.A = 0: one k = 2 product) */
+bool spasm_hip_certificate_rank_verify(const struct spasm_csr *A, const u8 *hash,
+                                       const struct spasm_rank_certificate *proof);                     /* spasm_certificate.c:101 */
+/* x.A == (x.L).U for a random x on the pivotal rows (spasm_prng_seed_simple(prime, seed, 0)) */
+bool spasm_hip_factorization_verify(const struct spasm_csr *A, const struct spasm_lu *fact, u64 seed);  /* spasm_certificate.c:165 */
+/* the same for count seeds at once (three k = count products, over A, L and U): correct[s] for seeds[s] */
+void spasm_hip_factorization_verify_batch(const struct spasm_csr *A, const struct spasm_lu *fact, int count, const u64 *seeds,
+                                          bool *correct);
+/* the reference's text format, byte for byte on save.  load: two deliberate differences -- the fifth line is read into j (the
+ * reference reads it into i again, spasm_certificate.c:258-259), and a file that ends early is refused (false) */
+void spasm_hip_rank_certificate_save(const struct spasm_rank_certificate *proof, FILE *f);             /* spasm_certificate.c:221 */
+bool spasm_hip_rank_certificate_load(FILE *f, struct spasm_rank_certificate *proof);                   /* spasm_certificate.c:242 */
+/* frees the four lists and the struct (what spasm_hip_certificate_rank_create returns) */
+void spasm_hip_rank_certificate_free(struct spasm_rank_certificate *proof);
 
 /* ======================================================================
  * (D) device-resident entry points

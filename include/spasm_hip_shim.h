@@ -38,6 +38,14 @@
 #define spasm_solve                   spasm_hip_solve
 #define spasm_gesv                    spasm_hip_gesv
 
+/* products x.A and rank certificates (spasm_spmv.c, spasm_certificate.c) */
+#define spasm_xApy                    spasm_hip_xApy
+#define spasm_certificate_rank_create spasm_hip_certificate_rank_create
+#define spasm_certificate_rank_verify spasm_hip_certificate_rank_verify
+#define spasm_factorization_verify    spasm_hip_factorization_verify
+#define spasm_rank_certificate_save   spasm_hip_rank_certificate_save
+#define spasm_rank_certificate_load   spasm_hip_rank_certificate_load
+
 /* containers, field, I/O (spasm_util.c, spasm_ZZp.c, spasm_triplet.c, spasm_transpose.c, spasm_io.c) */
 #define spasm_malloc                  spasm_hip_malloc
 #define spasm_calloc                  spasm_hip_calloc

@@ -2,7 +2,7 @@
 import ctypes as C
 import os
 
-from .matrix import CCsr, CTriplet, CLu, EchelonizeOpts, CDcsr, CSchurStats, CField
+from .matrix import CCsr, CTriplet, CLu, EchelonizeOpts, CDcsr, CSchurStats, CField, CCertificate
 
 # SPASM_HIP_LIB: load another build of the same library (A/B runs of a kernel variant)
 LIB_PATH = os.environ.get("SPASM_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libspasm_hip.so")
@@ -99,6 +99,18 @@ def lib():
         "spasm_hip_solver_destroy": (None, [vp]),
         "spasm_hip_solver_levels": (None, [vp, pint]),
         "spasm_hip_solver_stats": (ci, [vp, C.POINTER(C.c_double), ci]),
+        "spasm_hip_xApy_batch": (None, [pcsr, ci, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+        "spasm_hip_xApy": (None, [C.POINTER(C.c_int32), pcsr, C.POINTER(C.c_int32)]),
+        "spasm_hip_xApy_stats": (ci, [C.POINTER(C.c_double), ci]),
+        "spasm_hip_certificate_rank_create": (C.POINTER(CCertificate), [pcsr, C.POINTER(C.c_uint8), plu]),
+        "spasm_hip_certificate_rank_verify": (C.c_bool, [pcsr, C.POINTER(C.c_uint8), C.POINTER(CCertificate)]),
+        "spasm_hip_factorization_verify": (C.c_bool, [pcsr, plu, C.c_uint64]),
+        "spasm_hip_factorization_verify_batch": (None, [pcsr, plu, ci, C.POINTER(C.c_uint64), C.POINTER(C.c_bool)]),
+        "spasm_hip_rank_certificate_save": (None, [C.POINTER(CCertificate), vp]),
+        "spasm_hip_rank_certificate_load": (C.c_bool, [vp, C.POINTER(CCertificate)]),
+        "spasm_hip_rank_certificate_free": (None, [C.POINTER(CCertificate)]),
+        "spasm_hip_debug_prng": (None, [i64, C.c_uint64, C.c_uint32, ci, C.POINTER(C.c_int32)]),
+        "spasm_hip_debug_prng_hash": (None, [C.POINTER(C.c_uint8), i64, C.c_uint32, ci, C.POINTER(C.c_int32)]),
     }
     for name, (res, args) in sig.items():
         try:

@@ -11,7 +11,7 @@
 #include <vector>
 
 #include "device_types.h"
-#include "sha256.h"
+#include "prng.h"
 
 namespace sh {
 // device-resident dense / low-rank finish (dense_api.hip); false: not applicable, use the loops below
@@ -27,74 +27,6 @@ static int env_int_host(const char *name, int dflt)
 	return (e == nullptr || *e == 0) ? dflt : std::atoi(e);
 }
 
-// --------------------------------------------------------------------------
-// SHA-256 counter-mode generator (same stream as spasm_prng.c, so that seeded
-// runs draw the same coefficients as the reference)
-// --------------------------------------------------------------------------
-namespace sh {
-
-struct Prng {
-	uint8_t block[44];
-	uint8_t hash[32];
-	uint32_t prime, mask;
-	uint32_t counter;
-	int pos;
-
-	static void be32(uint8_t *dst, uint32_t v)
-	{
-		dst[0] = (uint8_t) (v >> 24);
-		dst[1] = (uint8_t) (v >> 16);
-		dst[2] = (uint8_t) (v >> 8);
-		dst[3] = (uint8_t) v;
-	}
-
-	void rehash()
-	{
-		Sha256 h;
-		h.reset();
-		h.update(block, 44);
-		h.finish(hash);
-		counter += 1;
-		be32(block + 36, counter);
-		pos = 0;
-	}
-
-	void seed(i64 p, uint64_t s, uint32_t seq)
-	{
-		std::memset(block, 0, sizeof(block));
-		be32(block + 0, (uint32_t) (s & 0xffffffffu));
-		be32(block + 4, (uint32_t) (s >> 32));
-		prime = (uint32_t) p;
-		i64 m = 1;
-		while (m < p)
-			m <<= 1;
-		mask = (uint32_t) (m - 1);
-		be32(block + 32, (uint32_t) p);
-		be32(block + 40, seq);
-		counter = 0;
-		rehash();
-	}
-
-	uint32_t next_u32()
-	{
-		if (pos == 8)
-			rehash();
-		const uint8_t *b = hash + 4 * pos;
-		pos += 1;
-		return ((uint32_t) b[0] << 24) | ((uint32_t) b[1] << 16) | ((uint32_t) b[2] << 8) | b[3];
-	}
-
-	spasm_ZZp next_zp()
-	{
-		for (;;) {
-			uint32_t x = next_u32() & mask;
-			if (x < prime)
-				return zp_init(prime, x);
-		}
-	}
-};
-
-}  // namespace sh
 
 extern "C" {
 

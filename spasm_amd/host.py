@@ -4,26 +4,29 @@ import ctypes as C
 import numpy as np
 
 from ._lib import lib, require_gpu
-from .matrix import Csr, Fact, CLu, EchelonizeOpts, view_csr, copy_csr
+from .matrix import Csr, Fact, CLu, CCertificate, EchelonizeOpts, view_csr, copy_csr
 
 _libc = C.CDLL(None)
 _libc.fopen.restype = C.c_void_p
 _libc.fopen.argtypes = [C.c_char_p, C.c_char_p]
 _libc.fclose.argtypes = [C.c_void_p]
+_libc.free.argtypes = [C.c_void_p]
 
 
 def _ip(a):
     return a.ctypes.data_as(C.POINTER(C.c_int))
 
 
-def load(path, prime, transpose_if_wide=False):
-    """spasm_triplet_load + spasm_compress (spasm_io.c:60, spasm_triplet.c:97) of an SMS / MatrixMarket file."""
+def load(path, prime, transpose_if_wide=False, with_hash=False):
+    """spasm_triplet_load + spasm_compress (spasm_io.c:60, spasm_triplet.c:97) of an SMS / MatrixMarket file.
+    with_hash: returns (A, hash), hash the 32-byte SHA-256 digest of the file that spasm_triplet_load computes (bytes)."""
     L = lib()
     f = _libc.fopen(path.encode(), b"r")
     if not f:
         raise OSError("cannot open %s" % path)
+    digest = (C.c_uint8 * 32)()
     try:
-        T = L.spasm_hip_triplet_load(f, prime, None)
+        T = L.spasm_hip_triplet_load(f, prime, digest if with_hash else None)
     finally:
         _libc.fclose(f)
     if transpose_if_wide and T.contents.n < T.contents.m:
@@ -32,7 +35,7 @@ def load(path, prime, transpose_if_wide=False):
     out = copy_csr(A)
     L.spasm_hip_csr_free(A)
     L.spasm_hip_triplet_free(T)
-    return out
+    return (out, bytes(digest)) if with_hash else out
 
 
 def compress(prime, n, m, ti, tj, tx):
@@ -373,3 +376,167 @@ def solve(F, b):
     finally:
         L.spasm_hip_csr_free(up)
     return x[:F.L.n], bool(ok)
+
+
+# ---- x.A and rank certificates (spasm_spmv.c, spasm_certificate.c; spasm_amd/csrc/spmv.hip, host_cert.cpp) ----
+
+def _i32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def xApy(X, A, Y=None):
+    """spasm_xApy (spasm_spmv.c:9) on the GPU: Y + X.A mod p, balanced.  X is one vector (A.n values) or a k x A.n batch (one
+    pass over A for all k); Y (same shape as the result, default zeros) is not modified."""
+    X = np.asarray(X)
+    one = X.ndim == 1
+    X = np.ascontiguousarray(X.reshape(1, -1) if one else X, np.int64)
+    if X.ndim != 2 or X.shape[1] != A.n:
+        raise ValueError("spasm_amd.xApy: X has shape %s, A has %d rows" % (X.shape, A.n))
+    k = X.shape[0]
+    if k > 64:
+        raise ValueError("spasm_amd.xApy: at most 64 vectors per call (%d)" % k)
+    Yout = np.zeros((k, A.m), np.int64) if Y is None else np.array(Y, np.int64).reshape(k, A.m)
+    require_gpu("xApy")
+    p = A.prime
+    Xc = np.ascontiguousarray(_balanced(X, p))
+    Yc = np.ascontiguousarray(_balanced(Yout, p))
+    a = view_csr(A)
+    lib().spasm_hip_xApy_batch(C.byref(a), k, _i32p(Xc) if Xc.size else None, _i32p(Yc) if Yc.size else None)
+    return Yc[0] if one else Yc
+
+
+def xApy_stats():
+    """spasm_hip_xApy_stats: the last x.A call's device ms (upload of A, its column-major image, the product), algorithmic bytes."""
+    out = (C.c_double * 8)()
+    lib().spasm_hip_xApy_stats(out, 8)
+    keys = ("upload_ms", "image_ms", "product_ms", "product_bytes", "k", "short_columns", "long_columns", "nnz")
+    return {k: out[t] for t, k in enumerate(keys)}
+
+
+def _balanced(v, p):
+    v = np.asarray(v, np.int64) % p
+    return np.where(v > p // 2, v - p, v).astype(np.int32)
+
+
+class Certificate:
+    """struct spasm_rank_certificate (spasm.h:110-118): rank r, modulus, the 32-byte hash of the input, pivot rows i, pivot
+    columns j, and the solutions x and y on the pivot rows (balanced)."""
+
+    def __init__(self, r, prime, hash, i, j, x, y):
+        self.r, self.prime, self.hash = int(r), int(prime), bytes(hash)
+        self.i, self.j = (np.ascontiguousarray(v, np.int32) for v in (i, j))
+        self.x, self.y = (np.ascontiguousarray(v, np.int32) for v in (x, y))
+        if len(self.hash) != 32:
+            raise ValueError("a certificate hash has 32 bytes")
+
+    def copy(self):
+        return Certificate(self.r, self.prime, self.hash, self.i.copy(), self.j.copy(), self.x.copy(), self.y.copy())
+
+    def __eq__(self, other):
+        return (isinstance(other, Certificate) and (self.r, self.prime, self.hash) == (other.r, other.prime, other.hash)
+                and all(np.array_equal(a, b) for a, b in zip((self.i, self.j, self.x, self.y), (other.i, other.j, other.x, other.y))))
+
+    def _c(self):
+        """a struct spasm_rank_certificate viewing this object's arrays (kept alive by the struct)"""
+        c = CCertificate()
+        c.r = self.r
+        c.prime = self.prime
+        C.memmove(c.hash, self.hash, 32)
+        arrays = tuple(np.ascontiguousarray(v if len(v) else np.zeros(1, np.int32), np.int32) for v in (self.i, self.j, self.x, self.y))
+        c._keep = arrays
+        c.i, c.j, c.x, c.y = (_i32p(v) for v in arrays)
+        return c
+
+    @staticmethod
+    def _of(c):
+        r = max(int(c.r), 0)
+        arr = lambda ptr: np.ctypeslib.as_array(ptr, shape=(r,)).copy() if r else np.zeros(0, np.int32)     # noqa: E731
+        return Certificate(c.r, c.prime, bytes(c.hash), arr(c.i), arr(c.j), arr(c.x), arr(c.y))
+
+    def save(self, path):
+        """spasm_rank_certificate_save (spasm_certificate.c:221): the reference's text format"""
+        c = self._c()
+        f = _libc.fopen(path.encode(), b"w")
+        if not f:
+            raise OSError("cannot open %s" % path)
+        try:
+            lib().spasm_hip_rank_certificate_save(C.byref(c), f)
+        finally:
+            _libc.fclose(f)
+
+    @staticmethod
+    def load(path):
+        """spasm_rank_certificate_load (spasm_certificate.c:242), the fifth line read into j; ValueError on a short file"""
+        L = lib()
+        f = _libc.fopen(path.encode(), b"r")
+        if not f:
+            raise OSError("cannot open %s" % path)
+        c = CCertificate()
+        try:
+            ok = L.spasm_hip_rank_certificate_load(f, C.byref(c))
+        finally:
+            _libc.fclose(f)
+        out = Certificate._of(c) if ok else None
+        for ptr in (c.i, c.j, c.x, c.y):
+            _libc.free(C.cast(ptr, C.c_void_p))
+        if out is None:
+            raise ValueError("%s is not a complete rank certificate" % path)
+        return out
+
+
+def _hash_arg(hash):
+    h = bytes(hash)
+    if len(h) != 32:
+        raise ValueError("the hash has 32 bytes (a SHA-256 digest), not %d" % len(h))
+    return (C.c_uint8 * 32).from_buffer_copy(h)
+
+
+def certificate_rank_create(A, hash, F):
+    """spasm_certificate_rank_create (spasm_certificate.c:21) on the GPU: F from echelonize with opts.L on A (the same matrix,
+    the same modulus), hash the 32-byte digest of the input (load(..., with_hash=True)).  Returns a Certificate."""
+    _check_solvable(F, A.m, A.prime, "certificate_rank_create")
+    if F.L.n != A.n:
+        raise ValueError("spasm_amd.certificate_rank_create: L has %d rows, A %d" % (F.L.n, A.n))
+    h = _hash_arg(hash)
+    require_gpu("certificate_rank_create")
+    L = lib()
+    a = view_csr(A)
+    lu, up, qinv = _lu_for(F, 0, 0)
+    try:
+        c = L.spasm_hip_certificate_rank_create(C.byref(a), h, C.byref(lu))
+    finally:
+        L.spasm_hip_csr_free(up)
+    out = Certificate._of(c.contents)
+    L.spasm_hip_rank_certificate_free(c)
+    return out
+
+
+def certificate_rank_verify(A, hash, cert):
+    """spasm_certificate_rank_verify (spasm_certificate.c:101) on the GPU: True iff cert proves the rank of A."""
+    h = _hash_arg(hash)
+    require_gpu("certificate_rank_verify")
+    a = view_csr(A)
+    c = cert._c()
+    return bool(lib().spasm_hip_certificate_rank_verify(C.byref(a), h, C.byref(c)))
+
+
+def factorization_verify(A, F, seeds=(42, 1337, 21011984)):
+    """spasm_factorization_verify (spasm_certificate.c:165) for every seed at once: x.A == (x.L).U for a random x on the pivotal
+    rows.  One seed: a bool; a sequence: a list of bools."""
+    one = np.ndim(seeds) == 0
+    s = np.atleast_1d(np.asarray(seeds, np.uint64))
+    _check_solvable(F, A.m, A.prime, "factorization_verify")
+    if F.L.n != A.n:
+        raise ValueError("spasm_amd.factorization_verify: L has %d rows, A %d" % (F.L.n, A.n))
+    require_gpu("factorization_verify")
+    L = lib()
+    a = view_csr(A)
+    lu, up, qinv = _lu_for(F, 0, 0)
+    ok = np.zeros(max(len(s), 1), np.bool_)
+    try:
+        L.spasm_hip_factorization_verify_batch(C.byref(a), C.byref(lu), len(s), s.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                               ok.ctypes.data_as(C.POINTER(C.c_bool)))
+    finally:
+        L.spasm_hip_csr_free(up)
+    res = [bool(v) for v in ok[:len(s)]]
+    return res[0] if one else res

@@ -73,6 +73,11 @@ class EchelonizeOpts(C.Structure):
                 ("low_rank_start_weight", C.c_double)]
 
 
+class CCertificate(C.Structure):    # struct spasm_rank_certificate, spasm.h:110-118
+    _fields_ = [("r", C.c_int), ("prime", C.c_int64), ("hash", C.c_uint8 * 32), ("i", C.POINTER(C.c_int)),
+                ("j", C.POINTER(C.c_int)), ("x", C.POINTER(C.c_int32)), ("y", C.POINTER(C.c_int32))]
+
+
 class CDcsr(C.Structure):          # spasm_hip_dcsr
     _fields_ = [("n", C.c_int), ("m", C.c_int), ("nnz", C.c_int64),
                 ("p", C.c_void_p), ("j", C.c_void_p), ("x", C.c_void_p)]
