@@ -48,12 +48,6 @@ constexpr int BS_PASSROWS = 32;
 #define BS_EMPTY_ENTRY uint4{(uint32_t) BS_RING, (uint32_t) BS_RING | ((uint32_t) BS_RING << 16), 0u, 0u}
 constexpr uint32_t BS_NONE = 0xFFFFFFFFu;
 
-int env_bs(const char *name, int dflt)
-{
-	const char *e = sh::env_get(name);
-	return (e == nullptr || *e == 0) ? dflt : std::atoi(e);
-}
-
 template <typename T> T *dalloc(int64_t count)
 {
 	return static_cast<T *>(sh::big_alloc((size_t) (count > 0 ? count : 1) * sizeof(T)));
@@ -82,7 +76,6 @@ struct BsArgs {
 	int plain;                    // coefficients (y) are plain residues (p < 2^16), not Montgomery form
 	int sparse_init;              // 1: the kernel scatters U_n itself (few entries); 0: R was pre-filled by bs_init_kernel
 	int r;
-	int dbg;                      // timing experiments only (SPASM_HIP_BS_DEBUG): bit 0/1/2 = skip phase A/B/C (wrong results)
 	unsigned long long *prof;     // SPASM_HIP_BS_PROFILE=1: 8 counters, shader-clock cycles of workgroup 0 per stage of a chunk, summed over the chunks
 	int sgn;                      // signed 16-bit entries (the SGN kernels); coefficients are negated balanced residues
 	MontDev F;
@@ -376,7 +369,7 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 
 		// ---- phase A: own row + dependencies outside the chunk, up to 3 * UNR loads in flight per lane ----
 		for (int pass = 0; pass < Geo::ITERS / Geo::UNR; pass++) {
-			if (pass * Geo::UNR * Geo::ROWS_PER_ITER >= nrows || (b.dbg & 1))
+			if (pass * Geo::UNR * Geo::ROWS_PER_ITER >= nrows)
 				break;
 			uint32_t acc[Geo::UNR], v0[Geo::UNR], v1[Geo::UNR];
 #pragma unroll
@@ -464,7 +457,7 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 		// holds everything a row with one or two dependencies inside the chunk needs, and the entry of the next trip is
 		// in flight during the arithmetic of this one.  (Every wave decodes every entry: the table is what keeps that cheap.)
 		{
-			const int niter = ((b.dbg & 2) ? 0 : ch.npass) * (PASSROWS / RSB);
+			const int niter = ch.npass * (PASSROWS / RSB);
 			uint4 e = (niter > 0) ? ptab[rsb] : EMPTY_ENTRY;
 			for (int it = 0; it < niter; it++) {
 				const uint4 e_next = (it + 1 < niter) ? ptab[(it + 1) * RSB + rsb] : EMPTY_ENTRY;
@@ -558,7 +551,7 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 		tick(4);          // phase B
 
 		// ---- phase C: write the chunk back ----
-		for (int s = slot0; s < ((b.dbg & 4) ? 0 : nrows); s += Geo::ROWS_PER_ITER)
+		for (int s = slot0; s < nrows; s += Geo::ROWS_PER_ITER)
 			if (lane_ok)
 				*row_at((uint32_t) (ch.lo + s)) = ring[s * RSTR + wl];
 		__syncthreads();          // (workgroup-scope release/acquire: later chunks read these rows; LDS metadata is free)
@@ -602,7 +595,9 @@ struct ApplyArgs {
 	int *Sj;
 	int *Sx;
 	int64_t cap;
-	int dbg;                      // timing experiments only (SPASM_HIP_BS_DEBUG): bit 3 = no loads of R, 4 = no look-back, 5 = no output stores
+	int dbg;                      // always 0 (bit 3 = no loads of R, 4 = no look-back, 5 = no output stores: timing experiments, wrong
+	                              // results).  Kept: bs_apply_s16_kernel measured ~3 % slower without the branches on it (close to its
+	                              // run-to-run spread; not settled)
 	int sgn;                      // R holds signed 16-bit entries (SgnDev)
 	SgnDev G;
 	unsigned long long *block_sum; // staged output: sum of the lengths of every block of SCAN_BLOCK rows (zeroed before the launch)
@@ -1213,7 +1208,6 @@ struct ExpandArgs {
 	int64_t cap;
 	const int *q;
 	SgnDev G;                     // (p, -p, p / 2: every format uses them)
-	int dbg;
 };
 
 // FMT 0: signed 16-bit entries, two per word; 1: residues in 16 bits, two per word; 2: residues, one per word
@@ -1241,16 +1235,6 @@ template <int FMT> __global__ __launch_bounds__(256) void bs_expand_kernel(Expan
 		const uint32_t *row = e.stage + (int64_t) k * e.nwords + lane;
 		int *oj = e.Sj + off, *ox = e.Sx + off;
 		uint32_t wpos = 0;
-		if (e.dbg & 128) {          // timing experiment: the same bytes as dense, contiguous stores (wrong results)
-			uint32_t acc = 0;
-			for (int t0 = 0; t0 < e.nwords; t0 += 64)
-				acc += row[t0];
-			for (int64_t t = lane; t < end - off; t += 64) {
-				oj[t] = (int) acc;
-				ox[t] = (int) acc;
-			}
-			continue;
-		}
 		// The loads of the next group are issued BEFORE the stores of this one: stores and loads share one in-order
 		// counter.  (No branch around the issue -- the wait counts are static; past the end the last group is read again.)
 		uint32_t wa[TU], wb[TU];
@@ -1512,8 +1496,8 @@ bool backsolve_eligible(int r, int Sm, int64_t nnz_u, int64_t *bytes, int64_t pr
 		return false;
 	// the apply kernels keep one row of S in LDS (96 KB); the one for signed 16-bit entries (p <= 44,927) goes through wider
 	// rows in segments
-	const bool segments = prime < 65536 && sgn_eligible(prime) && env_bs("SPASM_HIP_BS_SIGNED", 1) != 0 && true &&
-	                      env_bs("SPASM_HIP_BS_STAGED", 1) != 0 && (1) != 0;
+	const bool segments = prime < 65536 && sgn_eligible(prime) && env_int("SPASM_HIP_BS_SIGNED", 1) != 0 &&
+	                      env_int("SPASM_HIP_BS_STAGED", 1) != 0;
 	if (Sm > (segments ? 131072 : 24576))
 		return false;
 	if ((double) (nnz_u + r) * (double) Sm > 1.5e11)
@@ -1531,7 +1515,7 @@ void backsolve_plan(const FactPlan &P, spasm_hip_dfact *F, hipStream_t stream)
 	// p < 2^16: coefficients are kept as plain residues (the kernels multiply with 24-bit products + Barrett); small p: signed
 	// 16-bit entries of R, coefficients of the dependencies are NEGATED balanced residues (SgnDev above)
 	B.plain = P.prime < 65536;
-	B.sgn = B.plain && sgn_eligible(P.prime) && env_bs("SPASM_HIP_BS_SIGNED", 1) != 0 && true;
+	B.sgn = B.plain && sgn_eligible(P.prime) && env_int("SPASM_HIP_BS_SIGNED", 1) != 0;
 	// Shape of the build kernel (the plan is cut for it).  0 = 128-byte slab rows, 16 waves; 1 = 128 B, 8 waves; 2 = 64 B, 8
 	// waves; 3 = 32-byte slab rows (16 columns), 8 waves, passes of 64 rows, TWO workgroups per CU.  The build is a chain
 	// (DESIGN.md section 5): a workgroup takes the same time whatever the width of its slab, phase A being bound by the
@@ -1544,12 +1528,9 @@ void backsolve_plan(const FactPlan &P, spasm_hip_dfact *F, hipStream_t stream)
 		hipDeviceProp_t prop;
 		HIP_CHECK(hipGetDeviceProperties(&prop, dev));
 		cus = prop.multiProcessorCount;
-		const bool packed = B.sgn || (P.prime < 65536 && true);
+		const bool packed = P.prime < 65536;
 		const int slabs_small = packed ? (B.Sm + 31) / 32 : (B.Sm + 15) / 16;
-		const int slabs_narrow = (B.Sm + 15) / 16;
 		int shape = slabs_small <= (packed ? 2 * cus : cus) ? 2 : 0;
-		if (B.sgn && slabs_narrow <= 2 * cus && (0) != 0)
-			shape = 3;
 		// 4 / 5 = slabs of 10 / 12 words, as many waves as words (every wave ONE word of every row through phase B: passes of 64
 		// rows), chunks of 1,260 / 1,200 rows.  A workgroup's time is the vector work of its slab on ONE CU (phases A and B are
 		// ~61 and ~45 instructions per row and word) plus ~8,000 cycles of latency per chunk: narrower
@@ -1559,9 +1540,9 @@ void backsolve_plan(const FactPlan &P, spasm_hip_dfact *F, hipStream_t stream)
 		const int words = (B.Sm + 1) / 2;
 		// (twelve waves = three per SIMD on all four; ten leave two SIMDs with three and two with two, and the fuller ones set
 		//  the pace: 2.18 against 2.26 ms on mk13.b5, 2.66 for the 64-byte slabs of round 2)
-		if (B.sgn && (1) != 0 && (words + 11) / 12 <= cus)
+		if (B.sgn && (words + 11) / 12 <= cus)
 			shape = 5;
-		shape = env_bs("SPASM_HIP_BS_SHAPE", shape);
+		shape = env_int("SPASM_HIP_BS_SHAPE", shape);
 		if (shape >= 3 && !B.sgn)
 			shape = 2;
 		B.shape = shape;
@@ -1835,24 +1816,6 @@ void backsolve_plan(const FactPlan &P, spasm_hip_dfact *F, hipStream_t stream)
 		}
 	}
 
-	if ((0)) {
-		// shape of the plan (tuning aid)
-		int64_t cnt_hist[6] = {0, 0, 0, 0, 0, 0}, empty = 0;
-		for (size_t t = 0; t < ptab.size(); t++) {
-			const int c = (int) (ptab[t].x >> 16);
-			cnt_hist[c < 5 ? c : 5] += 1;
-			empty += c == 0;
-		}
-		int64_t far2 = 0, far1 = 0;
-		for (int c = 0; c < r; c++) {
-			far1 += far_head[c].x != BS_NONE;
-			far2 += far_head[c].z != BS_NONE;
-		}
-		fprintf(stderr, "[bs plan] r %d, Sm %d, levels %d, chunks %zu, passes %zu (%lld empty slots), rows with dependencies inside their chunk: 1: %lld, 2: %lld, 3: %lld, "
-		        "4: %lld, 5+: %lld; list %zu, far heads %lld + %lld, far rest %llu, np %zu\n",
-		        r, B.Sm, P.nlevels, chunks.size(), ptab.size() / PLAN_PASSROWS, (long long) empty, (long long) cnt_hist[1], (long long) cnt_hist[2], (long long) cnt_hist[3],
-		        (long long) cnt_hist[4], (long long) cnt_hist[5], near.size(), (long long) far1, (long long) far2, (unsigned long long) far_rp[r], np.size());
-	}
 	lap("chunks, passes, near and far tables");
 	B.nchunks = (int) chunks.size();
 	B.nnear = (int64_t) near.size();
@@ -1922,7 +1885,7 @@ void backsolve_build(const spasm_hip_dfact *F, hipStream_t stream)
 	if (!B.planned)
 		die("backsolve_build: the factor has no back-substitution plan");
 	// R is stored in 16 bits when the prime allows (42013, the reference's default, does): half the traffic, half the LDS
-	const bool packed = B.sgn || (F->prime < 65536 && true);
+	const bool packed = F->prime < 65536;
 	const int elem = packed ? 2 : 4;
 	const size_t bytes = (size_t) B.r * (size_t) B.ldR * (size_t) elem;
 	if (B.d_R != nullptr && B.elem_bytes != elem) {
@@ -1958,15 +1921,14 @@ void backsolve_build(const spasm_hip_dfact *F, hipStream_t stream)
 	b.sgn = B.sgn ? 1 : 0;
 	b.G = sgn_setup(F->prime);
 	b.F = to_dev(F->mont);
-	b.dbg = (0);
 	b.prof = nullptr;
-	if (env_bs("SPASM_HIP_BS_PROFILE", 0)) {
+	if (env_int("SPASM_HIP_BS_PROFILE", 0)) {
 		b.prof = dalloc<unsigned long long>(8);
 		HIP_CHECK(hipMemsetAsync(b.prof, 0, 8 * sizeof(unsigned long long), stream));
 	}
 	// few non-pivotal entries per row of U (mk13.b5: 0.08): the kernel scatters them into its LDS ring itself and R is
 	// neither zeroed nor read for them; many (factors that already hold dense rows): R is pre-filled instead
-	b.sparse_init = (B.nnp <= 4 * (int64_t) B.r && env_bs("SPASM_HIP_BS_SPARSE_INIT", 1) != 0) ? 1 : 0;
+	b.sparse_init = (B.nnp <= 4 * (int64_t) B.r && env_int("SPASM_HIP_BS_SPARSE_INIT", 1) != 0) ? 1 : 0;
 	HIP_CHECK(hipEventRecord(B.ev0, stream));
 	if (fresh || !b.sparse_init)        // (the padding columns beyond the last slab must be zero: once is enough for them)
 		HIP_CHECK(hipMemsetAsync(B.d_R, 0, bytes, stream));
@@ -2011,7 +1973,7 @@ void backsolve_build(const spasm_hip_dfact *F, hipStream_t stream)
 			launch_backsolve_variant<true, true, 16, 8>(b, B.Sm, stream, B);
 		else
 			launch_backsolve_variant<true, true, 32, 16>(b, B.Sm, stream, B);
-	} else if (B.plain) {          // (p < 2^16 with 32-bit entries of R: the SPASM_HIP_BS_PACKED=0 knob)
+	} else if (B.plain) {          // (p < 2^16 with 32-bit entries of R: no plan asks for them, every p < 2^16 is packed)
 		if (shape == 2)
 			launch_backsolve_variant<false, true, 16, 8>(b, B.Sm, stream, B);
 		else
@@ -2043,45 +2005,6 @@ void backsolve_build(const spasm_hip_dfact *F, hipStream_t stream)
 		fprintf(stderr, " total %.0f\n", (double) tot / B.nchunks);
 		sh::big_free(b.prof);
 	}
-	if ((0) && b.sparse_init && bytes < ((size_t) 1 << 30)) {
-		// debugging aid: the same build with R pre-filled (the other way of starting the rows), compared entry by entry
-		void *R2 = nullptr;
-		HIP_CHECK(sh::malloc_or_trim(&R2, bytes));
-		BsArgs c = b;
-		c.R = R2;
-		c.sparse_init = 0;
-		HIP_CHECK(hipMemsetAsync(R2, 0, bytes, stream));
-		if (packed)
-			hipLaunchKernelGGL(bs_init_kernel<uint16_t>, dim3((B.r + 255) / 256), dim3(256), 0, stream, c);
-		else
-			hipLaunchKernelGGL(bs_init_kernel<uint32_t>, dim3((B.r + 255) / 256), dim3(256), 0, stream, c);
-		if (B.sgn)
-			launch_backsolve_variant<true, true, 32, 16, true>(c, B.Sm, stream, B);
-		else if (packed)
-			launch_backsolve_variant<true, true, 32, 16>(c, B.Sm, stream, B);
-		else if (B.plain)
-			launch_backsolve_variant<false, true, 32, 16>(c, B.Sm, stream, B);
-		else
-			launch_backsolve_variant<false, false, 32, 16>(c, B.Sm, stream, B);
-		std::vector<unsigned char> h1(bytes), h2(bytes);
-		HIP_CHECK(hipMemcpyAsync(h1.data(), B.d_R, bytes, hipMemcpyDeviceToHost, stream));
-		HIP_CHECK(hipMemcpyAsync(h2.data(), R2, bytes, hipMemcpyDeviceToHost, stream));
-		HIP_CHECK(hipStreamSynchronize(stream));
-		int shown = 0;
-		int64_t bad = 0;
-		for (int64_t t = 0; t < (int64_t) B.r * B.ldR; t++) {
-			const uint32_t x1 = packed ? ((uint16_t *) h1.data())[t] : ((uint32_t *) h1.data())[t];
-			const uint32_t x2 = packed ? ((uint16_t *) h2.data())[t] : ((uint32_t *) h2.data())[t];
-			if (x1 != x2) {
-				bad += 1;
-				if (shown++ < 12)
-					fprintf(stderr, "[bs check] row %lld col %lld: sparse-init %u, pre-filled %u (r %d, Sm %d, ldR %lld, chunks %d)\n",
-					        (long long) (t / B.ldR), (long long) (t % B.ldR), x1, x2, B.r, B.Sm, (long long) B.ldR, B.nchunks);
-			}
-		}
-		fprintf(stderr, "[bs check] %lld entries differ\n", (long long) bad);
-		sh::big_free(R2);
-	}
 }
 
 // staged sparse output available for this factor?  *row_bytes = size of one packed row of the staging buffer
@@ -2089,7 +2012,7 @@ bool backsolve_stages_output(const spasm_hip_dfact *F, int64_t *row_bytes)
 {
 	const BsImage &B = F->bs;
 	*row_bytes = B.ldR * (B.valid ? B.elem_bytes : 4);          // (asked after the build: the entry size is known)
-	return B.planned && env_bs("SPASM_HIP_BS_STAGED", 1) != 0;
+	return B.planned && env_int("SPASM_HIP_BS_STAGED", 1) != 0;
 }
 
 // S rows from R: sparse rows into the pool of `a` (dense_out == nullptr) or dense rows.
@@ -2109,7 +2032,6 @@ void launch_backsolve_apply(const SchurArgs &a, const spasm_hip_dfact *F, uint32
 	d.Smpad = (int) B.ldR;
 	d.dense_out = dense_out;
 	d.ldS = ldS;
-	d.dbg = (0);
 	d.sgn = B.sgn ? 1 : 0;
 	d.G = sgn_setup(F->prime);
 	if (direct != nullptr && dense_out == nullptr) {
@@ -2189,7 +2111,7 @@ void launch_backsolve_apply(const SchurArgs &a, const spasm_hip_dfact *F, uint32
 		auto expand_slice = [&](int64_t r0, int n, const uint32_t *stage, const unsigned long long *block_sum, hipStream_t s2) {
 			const int nblocks = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
 			hipLaunchKernelGGL(bs_scan_lengths_kernel, dim3(nblocks), dim3(SCAN_BLOCK), 0, s2, a.row_len + r0, n, block_sum, direct->Sp + r0, direct->cap, a.ctr);
-			ExpandArgs e{stage, nwords, n, direct->Sp + r0, direct->Sj, direct->Sx, direct->cap, a.q, d.G, d.dbg};
+			ExpandArgs e{stage, nwords, n, direct->Sp + r0, direct->Sj, direct->Sx, direct->cap, a.q, d.G};
 			const int blocks3 = std::max(1, std::min((n + 3) / 4, prop.multiProcessorCount * 8));
 			if (B.sgn)
 				hipLaunchKernelGGL(bs_expand_kernel<0>, dim3(blocks3), dim3(256), 0, s2, e);

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <thread>
 
 #include "../../include/spasm_hip.h"
 
@@ -14,15 +15,18 @@ namespace sh {
 
 // Fatal error: same contract as the reference's err()/errx() use -- message on
 // stderr, then exit(1).  The product never falls back to a CPU path.
-[[noreturn]] inline void die(const char *fmt, ...)
+// On a thread the library started itself (library_thread) the process ends with _Exit(1) after a flush instead: exit() there
+// would run the static destructors, the HIP runtime's among them, while the caller's thread is still inside HIP.
+[[noreturn]] void die(const char *fmt, ...);
+
+// std::thread(fn, args...), marked as one of the library's own threads for die()
+void mark_library_thread();
+template <typename Fn, typename... Args> std::thread library_thread(Fn &&fn, Args... args)
 {
-	va_list ap;
-	va_start(ap, fmt);
-	std::fprintf(stderr, "[spasm-hip] fatal: ");
-	std::vfprintf(stderr, fmt, ap);
-	std::fprintf(stderr, "\n");
-	va_end(ap);
-	std::exit(1);
+	return std::thread([fn = std::forward<Fn>(fn), args...]() mutable {
+		mark_library_thread();
+		fn(args...);
+	});
 }
 
 inline void *xmalloc(int64_t bytes)
@@ -47,6 +51,8 @@ double wtime();
 // selects an experiment, a debugging aid or a code path kept for A/B runs and tests, and is only honoured when
 // SPASM_HIP_EXPERIMENT=1 is set as well (tests/conftest.py sets it).  Returns the value or nullptr.
 const char *env_get(const char *name);
+// env_get(name) as an integer; dflt when unset or empty
+int env_int(const char *name, int dflt);
 // fn(0) .. fn(ntasks - 1) on the library's worker threads and the caller (host_util.cpp); returns when all are done
 void pool_run(int ntasks, const std::function<void(int)> &fn);
 

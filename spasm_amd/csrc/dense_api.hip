@@ -46,12 +46,6 @@ using namespace sh;
 
 namespace {
 
-int env_int(const char *name, int dflt)
-{
-	const char *e = sh::env_get(name);
-	return (e == nullptr || *e == 0) ? dflt : std::atoi(e);
-}
-
 template <typename T> T *dalloc(int64_t count)
 {
 	return static_cast<T *>(sh::big_alloc((size_t) (count > 0 ? count : 1) * sizeof(T)));
@@ -259,7 +253,7 @@ void device_random_dense_rows(const spasm_hip_dcsr &dA, const int *d_rows, int n
 	unsigned long long *dY = (unsigned long long *) big_alloc((size_t) N * (size_t) m * sizeof(unsigned long long));
 	HIP_CHECK(hipMemsetAsync(dY, 0, (size_t) N * m * sizeof(unsigned long long), stream));
 	launch_combine(dA.p, dA.j, dA.x, d_rows, n, N, w, m, salt, dY, F->mont, stream, colmap, base, dA.nnz);
-	if (compact && (1) != 0) {
+	if (compact) {
 		// the rows combined hold non-pivotal columns only: their combinations, reduced mod p, ARE the dense rows on those columns
 		// (mk15.b4: 20-26 ms per 4,096 combinations through count / scan / pack / the elimination kernels, of a finish of 100)
 		launch_dense_reduce_rows(dY, N, m, F->mont, d_S, ldS, stream);
@@ -305,7 +299,7 @@ void device_random_dense_rows(const spasm_hip_dcsr &dA, const int *d_rows, int n
 	// a few very long rows: cut into pieces that are reduced side by side and added up (launch_split_rows)
 	const int Sm = F->Sm;
 	int pieces = 1;
-	if (N <= 64 && ynnz / N >= 8192 && (1) != 0)
+	if (N <= 64 && ynnz / N >= 8192)
 		pieces = (int) std::min<i64>(std::min<i64>(64, W->max_rows / N), (ynnz / N + 2047) / 2048);
 	if (pieces > 1) {
 		const int NP = N * pieces;
@@ -469,13 +463,12 @@ bool finish_on_device(const struct spasm_csr *A, const int *p, int n, struct spa
 	double t_rows = 0.0, t_rref = 0.0;
 	// Wide remainders (tens of thousands of columns, rank a few thousand): the rows are added by ROW panels
 	// (device_echelon_extend: one pass over the stack per 64 pivots, E is not factored again); narrow ones go through the
-	// column-panel RREF of the whole stack [E; Y], which is at its best there.  SPASM_HIP_ROW_PANELS=0/1 forces the choice.
-	const int rp_env = (-1);
-	const bool row_panels = prime <= 65279 && (rp_env > 0 || (rp_env < 0 && Sm0 >= (16384)));
-	const bool row_panels_later = prime <= 65279 && rp_env != 0 && (1) != 0;
+	// column-panel RREF of the whole stack [E; Y], which is at its best there, until they hold echelon rows (k > 0): the rows
+	// added after that go by row panels too.
+	const bool row_panels = prime <= 65279 && Sm0 >= 16384;
 	auto stack_and_reduce = [&](int rows_added) {
 		const double t0 = wtime();
-		const int rk = (row_panels || (row_panels_later && k > 0)) ? device_echelon_extend(prime, Sm0, dM, ld, k, rows_added, dpiv, stream)
+		const int rk = (row_panels || (prime <= 65279 && k > 0)) ? device_echelon_extend(prime, Sm0, dM, ld, k, rows_added, dpiv, stream)
 		                          : spasm_hip_drref(prime, k + rows_added, Sm0, dM, ld, dpiv, stream);
 		t_rref += wtime() - t0;
 		const int rr = rk - k;
@@ -514,7 +507,7 @@ bool finish_on_device(const struct spasm_csr *A, const int *p, int n, struct spa
 		const int *rows_left = drows + processed;
 		// (rows of a Schur complement by this very factor hold non-pivotal columns only -- checked, once: the accumulators of the
 		//  combinations then span Sm columns instead of m)
-		const bool compact = m > 2 * Sm0 && (1) != 0 &&
+		const bool compact = m > 2 * Sm0 &&
 		                     rows_are_nonpivotal(dA.p, dA.j, rows_left, nleft, F->d_lab, (uint32_t) F->rpad, stream);
 		rank_ub = std::min(nleft, Sm0 - k);
 		int w = (opts->low_rank_start_weight < 0) ? (int) std::ceil(-std::log(0.01) * nleft / (rank_ub > 0 ? rank_ub : 1))
@@ -777,7 +770,7 @@ int spasm_hip_ffpack_rref(i64 prime, int n, int m, void *A, int ldA, spasm_datat
 		}
 		std::vector<std::thread> pool;
 		for (int t = 0; t < nt; t++)
-			pool.emplace_back([&, t]() { body((int) ((i64) nrows * t / nt), (int) ((i64) nrows * (t + 1) / nt)); });
+			pool.push_back(library_thread([&, t]() { body((int) ((i64) nrows * t / nt), (int) ((i64) nrows * (t + 1) / nt)); }));
 		for (auto &th : pool)
 			th.join();
 	};

@@ -2458,10 +2458,8 @@ int device_rref(int64_t prime, int n, int m, uint32_t *dA, int64_t ld, int *d_pi
 				signed char *Mh_s = M8 + (size_t) slot * 2 * (size_t) n * 64, *Ml_s = Mh_s + (size_t) n * 64;
 				MultArgs ma{dA, ld, n, m, c0, Ginv + (size_t) par * NB * NB, gamma + par * NB, knew_s, P_s, F, rho_s, cand_pivot + par * NB, mfma_ok ? Mh_s : nullptr, mfma_ok ? Ml_s : nullptr,
 				            mfma_ok ? Zacc + (size_t) nsets * NB : nullptr /* M_s becomes block `nsets` of Z */, ldz, abort_c,
-				            take_what_comes ? flags : nullptr, abort_d, nsets};
-				ma.wait_word = (phase == 2) ? hand_try + nsets : nullptr;
-				ma.wait_word2 = (phase == 2 && look_follows) ? hand_look + nsets : nullptr;
-				ma.wait_value2 = LOOK_WGS;
+				            take_what_comes ? flags : nullptr, abort_d, nsets, (phase == 2) ? hand_try + nsets : nullptr,
+				            (phase == 2 && look_follows) ? hand_look + nsets : nullptr, LOOK_WGS};
 				const int nmult = (n + 63) / 64;
 				// the columns of the super-panel, from this panel on, and (matrix cores) the multipliers of its earlier
 				// panels, blocks 0 .. nsets - 1 of Z: K = 64 update now

@@ -21,13 +21,6 @@ bool finish_on_device(const struct spasm_csr *A, const int *p, int n, struct spa
 
 using namespace sh;
 
-static int env_int_host(const char *name, int dflt)
-{
-	const char *e = sh::env_get(name);
-	return (e == nullptr || *e == 0) ? dflt : std::atoi(e);
-}
-
-
 extern "C" {
 
 // exported for the tests: the first `count` values of the stream (prime, seed, seq)
@@ -394,7 +387,7 @@ extern "C" struct spasm_lu *spasm_hip_echelonize(const struct spasm_csr *A0, str
 		{
 			Stopwatch sw(3);
 			// the entries of S stay on the device until somebody needs them on the host (see below)
-			resident_lazy_downloads(round + 1 < opts->max_round && (1) != 0);
+			resident_lazy_downloads(round + 1 < opts->max_round);
 			S = spasm_hip_schur(A, p + npiv, n - npiv, fact, density, fact->Ltmp, p_in, p_out);
 			resident_lazy_downloads(false);
 		}
@@ -416,10 +409,8 @@ extern "C" struct spasm_lu *spasm_hip_echelonize(const struct spasm_csr *A0, str
 		// The remainder goes to the finishing code as it would have, with no pivots of its own: same row space.
 		const int census = (round + 1 < opts->max_round) ? resident_fl_census(A) : -1;
 		// (the factor 8 is the largest ratio (pivots of a whole search) / (its first step) seen on the generated families, where it is
-		//  1.1-1.5; a matrix whose greedy step finds ten times what its leftmost entries give would be cut short here:
-		//  SPASM_HIP_CENSUS_FACTOR raises it, 0 switches the short cut off -- the round then runs and decides by itself)
-		const double census_factor = (double) (8);
-		if (census >= 0 && census_factor > 0 && census_factor * census < opts->min_pivot_proportion * std::min(n, m - U->n)) {
+		//  1.1-1.5; a matrix whose greedy step finds ten times what its leftmost entries give would be cut short here)
+		if (census >= 0 && 8.0 * census < opts->min_pivot_proportion * std::min(n, m - U->n)) {
 			logmsg("[echelonize] %d leftmost-entry pivots in the Schur complement (counted on the device): not enough for another round\n", census);
 			npiv = 0;
 			for (int i = 0; i < n; i++)

@@ -130,7 +130,7 @@ struct Search {
 		};
 		std::vector<std::thread> pool;
 		for (int t = 1; t < T; t++)
-			pool.emplace_back(scan, (int) ((i64) n * t / T), (int) ((i64) n * (t + 1) / T));
+			pool.push_back(library_thread(scan, (int) ((i64) n * t / T), (int) ((i64) n * (t + 1) / T)));
 		scan(0, (int) ((i64) n / T));
 		for (auto &th : pool)
 			th.join();
@@ -174,7 +174,7 @@ struct Search {
 			auto in_threads = [&](auto &&body) {
 				std::vector<std::thread> pool;
 				for (int t = 1; t < T; t++)
-					pool.emplace_back(body, (int) ((i64) A->n * t / T), (int) ((i64) A->n * (t + 1) / T));
+					pool.push_back(library_thread(body, (int) ((i64) A->n * t / T), (int) ((i64) A->n * (t + 1) / T)));
 				body(0, (int) ((i64) A->n / T));
 				for (auto &th : pool)
 					th.join();
@@ -608,7 +608,7 @@ struct Search {
 		};
 		std::vector<std::thread> pool;
 		for (int t = 0; t < T; t++)
-			pool.emplace_back(worker);
+			pool.push_back(library_thread(worker));
 		for (auto &th : pool)
 			th.join();
 		if (sh::env_get("SPASM_HIP_PIVOT_STATS"))
@@ -643,7 +643,7 @@ struct Search {
 		const int T = (npiv < 20000) ? 1 : std::max(1, std::min(8, usable_cpus()));
 		std::vector<std::thread> pool;
 		for (int t = 1; t < T; t++)
-			pool.emplace_back(check, (int) ((i64) npiv * t / T), (int) ((i64) npiv * (t + 1) / T));
+			pool.push_back(library_thread(check, (int) ((i64) npiv * t / T), (int) ((i64) npiv * (t + 1) / T)));
 		check(0, (int) ((i64) npiv / T));
 		for (auto &th : pool)
 			th.join();
@@ -691,7 +691,7 @@ struct Search {
 			const int T = (npiv < 20000) ? 1 : std::max(1, std::min(8, usable_cpus()));
 			std::vector<std::thread> pool;
 			for (int t = 1; t < T; t++)
-				pool.emplace_back(fill, (int) ((i64) n * t / T), (int) ((i64) n * (t + 1) / T));
+				pool.push_back(library_thread(fill, (int) ((i64) n * t / T), (int) ((i64) n * (t + 1) / T)));
 			fill(0, (int) ((i64) n / T));
 			for (auto &th : pool)
 				th.join();
@@ -784,7 +784,7 @@ extern "C" int spasm_hip_pivots_extract_structural(const struct spasm_csr *A, co
 			    resident_prefetch_possible() && usable_cpus() > 1)
 			{
 				const int dev = resident_current_device();
-				upload = std::thread([A, dev]() { resident_prefetch_matrix(A, dev); });
+				upload = library_thread([A, dev]() { resident_prefetch_matrix(A, dev); });
 			}
 		}
 		struct Joiner {
@@ -950,7 +950,7 @@ extern "C" int spasm_hip_pivots_extract_structural(const struct spasm_csr *A, co
 	auto in_threads = [&](auto &&body) {
 		std::vector<std::thread> pool;
 		for (int t = 1; t < T_rows; t++)
-			pool.emplace_back(body, (int) ((i64) npiv * t / T_rows), (int) ((i64) npiv * (t + 1) / T_rows));
+			pool.push_back(library_thread(body, (int) ((i64) npiv * t / T_rows), (int) ((i64) npiv * (t + 1) / T_rows)));
 		body(0, (int) ((i64) npiv / T_rows));
 		for (auto &th : pool)
 			th.join();

@@ -16,6 +16,27 @@
 
 namespace sh {
 
+namespace {
+thread_local bool t_library_thread = false;
+}  // namespace
+
+void mark_library_thread() { t_library_thread = true; }
+
+void die(const char *fmt, ...)
+{
+	va_list ap;
+	va_start(ap, fmt);
+	std::fprintf(stderr, "[spasm-hip] fatal: ");
+	std::vfprintf(stderr, fmt, ap);
+	std::fprintf(stderr, "\n");
+	va_end(ap);
+	if (t_library_thread) {
+		std::fflush(nullptr);
+		std::_Exit(1);
+	}
+	std::exit(1);
+}
+
 double wtime()
 {
 	struct timeval tv;
@@ -81,7 +102,7 @@ void pool_run(int ntasks, const std::function<void(int)> &fn)
 		g_pool = new WorkerPool();
 		g_pool->nworkers = std::max(0, std::min(15, usable_cpus() - 1));
 		for (int t = 0; t < g_pool->nworkers; t++)
-			std::thread([] { t_in_pool_job = true; g_pool->worker(); }).detach();
+			library_thread([] { t_in_pool_job = true; g_pool->worker(); }).detach();
 	});
 	WorkerPool &P = *g_pool;
 	if (ntasks == 1 || P.nworkers == 0 || t_in_pool_job || !P.one_job.try_lock()) {
@@ -136,6 +157,12 @@ const char *env_get(const char *name)
 		return nullptr;
 	}
 	return v;
+}
+
+int env_int(const char *name, int dflt)
+{
+	const char *e = env_get(name);
+	return (e == nullptr || *e == 0) ? dflt : std::atoi(e);
 }
 
 int verbose()

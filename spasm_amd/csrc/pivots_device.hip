@@ -101,12 +101,6 @@ struct PsCtrl {
 
 #define RLX_AGENT __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT
 
-int env_int(const char *name, int dflt)
-{
-	const char *e = sh::env_get(name);
-	return (e == nullptr || *e == 0) ? dflt : std::atoi(e);
-}
-
 __device__ __forceinline__ int ld_i32(const int *p) { return __hip_atomic_load(p, RLX_AGENT); }
 __device__ __forceinline__ u64 ld_u64(const u64 *p) { return __hip_atomic_load(p, RLX_AGENT); }
 __device__ __forceinline__ void st_i32(int *p, int v) { __hip_atomic_store(p, v, RLX_AGENT); }
@@ -1485,7 +1479,7 @@ int device_acyclic_greedy(const struct spasm_csr *A, int *pinv, int *qinv, std::
 	while (per_cu_labels > 1 && (size_t) cus * per_cu_labels * per_search_labels > ((size_t) 16 << 30))
 		per_cu_labels -= 1;
 	// (behind the labelled search the ticket search gets a fraction of the rows: 512 searches at a time are plenty)
-	const int grid = labels ? std::min(cus * per_cu, std::max(64, (512))) : cus * per_cu;
+	const int grid = labels ? std::min(cus * per_cu, 512) : cus * per_cu;
 	const int grid_labels = cus * per_cu_labels, grid_max = std::max(grid, labels ? grid_labels : 0);
 	std::vector<void *> owned;
 	auto dal = [&](size_t bytes) {
@@ -1792,8 +1786,7 @@ int device_acyclic_greedy(const struct spasm_csr *A, int *pinv, int *qinv, std::
 		// (without the chase: a sweep moves the labels one level down the chains that hang under the pivots of the ticket search: a dozen of them on
 		//  mk15.b4 -- 64-330 sweeps, 4-15 ms, against 35 + 8 ms of depth-first search and check on the host --, three thousand
 		//  on mk15.b5 -- 6,700 sweeps, 0.87 s: given up after 30 ms, the host then orders as before)
-		const int limit = (16384);
-		while (!settled && sweeps >= 0 && sweeps < limit && wtime() - tl < patience) {
+		while (!settled && sweeps >= 0 && sweeps < 16384 && wtime() - tl < patience) {
 			HIP_CHECK(hipMemsetAsync(d_changed_final, 0, sizeof(int), stream));
 			for (int t = 0; t < 8; t++)
 				hipLaunchKernelGGL(pivot_labels_relax_kernel, dim3((m + 255) / 256), dim3(256), 0, stream, dA.p, dA.j, d_qinv, m, lab, d_changed_final);

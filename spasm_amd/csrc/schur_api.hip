@@ -19,7 +19,7 @@
 namespace sh {
 void launch_schur_lds(const SchurArgs &a, int table, bool wide, int blocks, hipStream_t stream);
 size_t schur_lds_bytes(int table, bool wide);
-void launch_finalize(const spasm_hip_dwork *W, int nrows, int sort_rows, hipStream_t stream);
+void launch_finalize(const spasm_hip_dwork *W, int nrows, hipStream_t stream);
 void wave_dense_geometry(int rpad, int Sm, bool wide, int64_t *slot_bytes, int64_t *off_bm, int64_t *off_xn);
 void group_geometry(int rpad, int Sm, bool wide, int64_t *slot_bytes, int64_t *off_bm);
 int64_t regroup_scratch_ints(int nrows, int r);
@@ -66,12 +66,6 @@ int comm_world(const spasm_hip_comm *c);
 using namespace sh;
 
 namespace {
-
-int env_int(const char *name, int dflt)
-{
-	const char *e = sh::env_get(name);
-	return (e == nullptr || *e == 0) ? dflt : std::atoi(e);
-}
 
 template <typename T> T *dalloc(int64_t count)
 {
@@ -132,12 +126,10 @@ void *big_alloc(size_t bytes)
 		// the call, which depends on timing, and differ by tens of percent from one call to the next.  With exact sizes and a
 		// window of 1.5x the third mk15.b4 call of a process still fetched 62 GB from the device (3.5 s inside one sparse round;
 		// spasm_hip_echelonize_counters: block_cache_miss_bytes), the fourth 21 GB.
-		static const bool classes = (1) != 0;
 		size_t step = (size_t) 1 << 20;
 		while ((step << 4) <= bytes)
 			step <<= 1;
-		if (classes)
-			bytes = (bytes + step - 1) / step * step;
+		bytes = (bytes + step - 1) / step * step;
 		std::lock_guard<std::mutex> guard(g_big.mutex);
 		int best = -1;
 		for (size_t t = 0; t < g_big.free_blocks.size(); t++) {
@@ -152,7 +144,7 @@ void *big_alloc(size_t bytes)
 			// (round 6: bounded again, at four times the size or 8 GB more, whichever is larger -- a 300 MB buffer could pin a 19 GB block
 			//  for its lifetime and send the next 19 GB request to the device for 28 GB fresh; the bench's case above, a 9 GB request
 			//  that finds 19 GB parked, still fits)
-			const size_t most = !classes ? bytes + bytes / 2 : (bytes >= ((size_t) 256 << 20) ? std::max(4 * bytes, bytes + ((size_t) 8 << 30)) : 2 * bytes);
+			const size_t most = bytes >= ((size_t) 256 << 20) ? std::max(4 * bytes, bytes + ((size_t) 8 << 30)) : 2 * bytes;
 			if (have >= bytes && have <= most && (best < 0 || have < g_big.free_blocks[(size_t) best].second))
 				best = (int) t;
 		}
@@ -416,7 +408,7 @@ static std::vector<ResidentEntry> g_resident;
 // factor image in 0.7 or 19 ms (`factor_image_ms` 6.8 or 30 from one bench process to the next -- with the same library).  Copies of
 // 256 KB and more go through pinned buffers of the library instead: 8 MB pieces, filled by up to four threads (each with two
 // buffers of its own, so that a piece is on its way while the next one is filled), sent by hipMemcpyAsync on the caller's
-// stream.  The source is consumed when the call returns.  SPASM_HIP_STAGED_H2D=0: the runtime's own path.
+// stream.  The source is consumed when the call returns.
 namespace {
 constexpr size_t H2D_PIECE = (size_t) 8 << 20;
 constexpr int H2D_THREADS = 4;
@@ -437,8 +429,7 @@ void h2d(void *dst, const void *src, size_t bytes, hipStream_t stream)
 {
 	if (bytes == 0)
 		return;
-	static const bool staged = (1) != 0;
-	if (!staged || bytes < ((size_t) 256 << 10)) {
+	if (bytes < ((size_t) 256 << 10)) {
 		HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream));
 		return;
 	}
@@ -478,7 +469,7 @@ void h2d(void *dst, const void *src, size_t bytes, hipStream_t stream)
 	};
 	std::vector<std::thread> pool;
 	for (int t = 1; t < T; t++)
-		pool.emplace_back(work, t);
+		pool.push_back(library_thread(work, t));
 	work(0);
 	for (auto &th : pool)
 		th.join();
@@ -511,8 +502,7 @@ void d2h(void *dst, const void *src, size_t bytes, hipStream_t stream)
 {
 	if (bytes == 0)
 		return;
-	static const bool staged = (1) != 0;
-	bool direct = !staged || bytes < ((size_t) 256 << 10) || bytes > ((size_t) 256 << 20);
+	bool direct = bytes < ((size_t) 256 << 10) || bytes > ((size_t) 256 << 20);
 	std::unique_lock<std::mutex> guard(g_h2d.mutex, std::defer_lock);
 	if (!direct) {
 		guard.lock();
@@ -557,7 +547,7 @@ void d2h(void *dst, const void *src, size_t bytes, hipStream_t stream)
 	};
 	std::vector<std::thread> pool;
 	for (int t = 1; t < T; t++)
-		pool.emplace_back(work, t);
+		pool.push_back(library_thread(work, t));
 	work(0);
 	for (auto &th : pool)
 		th.join();
@@ -594,16 +584,14 @@ void resident_end()
 	// is erratic on these boxes -- 0.1 to 1 s apiece, now and then -- and made five of eight consecutive mk14.b4 calls take
 	// 1.0-2.3 s instead of 0.55 (keeping 32 or 64 GB did not help: whatever is handed back comes back slowly).
 	// spasm_hip_release_cached_memory() gives everything back; a failed hipMalloc of the library's own does too (big_alloc).
-	if ((0) == 0) {
-		// (default: a third of the device memory, at most the cap of the cache -- a quarter, 72 GB here, was tried in round 4 and is
-		//  less than one mk15.b4 call parks: every call then gave 10-20 GB back and paid 1-2 s to get them again, in whichever
-		//  stage asked first --; and whatever sat unused through two calls in a row goes back whatever the total)
-		size_t free_b = 0, total_b = 0;
-		HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
-		const int dflt = (int) std::min<size_t>(96, (total_b >> 30) / 3);
-		big_age((2));
-		big_trim((size_t) std::max(0, env_int("SPASM_HIP_KEEP_GB", dflt)) << 30);
-	}
+	// (default: a third of the device memory, at most the cap of the cache -- a quarter, 72 GB here, was tried in round 4 and is
+	//  less than one mk15.b4 call parks: every call then gave 10-20 GB back and paid 1-2 s to get them again, in whichever
+	//  stage asked first --; and whatever sat unused through two calls in a row goes back whatever the total)
+	size_t free_b = 0, total_b = 0;
+	HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+	const int dflt = (int) std::min<size_t>(96, (total_b >> 30) / 3);
+	big_age(2);
+	big_trim((size_t) std::max(0, env_int("SPASM_HIP_KEEP_GB", dflt)) << 30);
 }
 
 void resident_counters(i64 *uploads, i64 *hits)
@@ -869,7 +857,7 @@ DeviceMatrix::DeviceMatrix(const struct spasm_csr *A, hipStream_t stream, bool s
 	HIP_CHECK(hipStreamSynchronize(stream));
 	g_resident_uploads += 1;
 	if (g_resident_on) {
-		g_resident.push_back(ResidentEntry{A, p, j, x, nnz});
+		g_resident.push_back(ResidentEntry{A, p, j, x, nnz, false});
 		owned = false;
 	} else {
 		owned = true;
@@ -1152,8 +1140,7 @@ static bool heights_from_hint(const struct spasm_csr *U, const int *qinv, std::v
 	const int r = U->n;
 	{
 		std::lock_guard<std::mutex> guard(sh::g_level_hint_mutex);
-		if (sh::g_level_hint.U != (const void *) U || sh::g_level_hint.rows != r || (int) sh::g_level_hint.height.size() != r || r < 20000 ||
-		    (1) == 0)
+		if (sh::g_level_hint.U != (const void *) U || sh::g_level_hint.rows != r || (int) sh::g_level_hint.height.size() != r || r < 20000)
 			return false;
 		height = sh::g_level_hint.height;
 	}
@@ -1614,7 +1601,7 @@ spasm_hip_dfact *spasm_hip_dfact_create(const struct spasm_csr *U, const int *qi
 	const bool plan_sparse = sparse_image_possible(F->prime) && r > 0 && m - r > 0 &&
 	                         (env_int("SPASM_HIP_SPARSE_IMAGE", -1) == 1 || (m - r >= 8192 && (double) r * (double) (m - r) >= 5e8));
 	// (large factors: by a thread of their own, started below once the plan stands where it will stay)
-	const bool plan_sparse_async = plan_sparse && r >= 100000 && (1) != 0;
+	const bool plan_sparse_async = plan_sparse && r >= 100000;
 	if (plan_sparse && !plan_sparse_async)
 		sparse_image_plan(P, F, stream);
 	const double t_bs = wtime();
@@ -1622,7 +1609,7 @@ spasm_hip_dfact *spasm_hip_dfact_create(const struct spasm_csr *U, const int *qi
 		logmsg("[factor image] tables of the sparse image: %.1f ms\n", 1e3 * (t_bs - t_uploaded));
 	int64_t bs_bytes = 0;
 	if (env_int("SPASM_HIP_BACKSOLVE", -1) != 0 && backsolve_eligible(r, m - r, F->nnz, &bs_bytes, F->prime)) {
-		if (plan_sparse && env_int("SPASM_HIP_BACKSOLVE", -1) != 1 && (0) == 0) {
+		if (plan_sparse && env_int("SPASM_HIP_BACKSOLVE", -1) != 1) {
 			// the plan of the dense image waits for a batch that wants it (backsolve_build); what the path choice reads is known now
 			F->bs.r = r;
 			F->bs.Sm = m - r;
@@ -1823,15 +1810,14 @@ int dschur_impl(const spasm_hip_dcsr *A, const int *d_rows, int nrows, const spa
 	// ... and in the dense accumulators: a column receives at most maxdeg + 1 terms, each below 2p (the
 	// row-group kernel adds unreduced products)
 	bool wide_dense = false;          // (set below, once it is known that a row-by-row path runs: it needs the tables of ensure_row_tables)
-	const int sort_rows = (1);
 	const int small_table = 1024, big_table = 8192;
 	const int cus = cu_count();
 	// tests: 1 = start at the large LDS table, 2 = dense accumulators only.  The large table is otherwise
-	// skipped (one wave per CU: slower than the dense tier) unless SPASM_HIP_USE_BIG_TABLE=1.
+	// skipped (one wave per CU: slower than the dense tier).
 	int force_tier = env_int("SPASM_HIP_FORCE_TIER", 0);
 	if (Lout != nullptr)
 		force_tier = 2;         // rows must not be restarted once coefficients have been recorded: no LDS tiers
-	const bool use_big = (force_tier == 1) || (0);
+	const bool use_big = force_tier == 1;
 
 	// row-group kernel (64 consecutive rows per wave, label-major state) for every row: default for
 	// batches large enough to fill the GPU with groups; SPASM_HIP_GROUP=0/1 forces the choice.
@@ -1858,14 +1844,14 @@ int dschur_impl(const spasm_hip_dcsr *A, const int *d_rows, int nrows, const spa
 	if (!want_bs && !want_sp) {
 		// (the components of the pivot graph are what the row-GROUP kernel regroups its rows by: a density sample of 100 rows on the
 		//  per-row tiers only needs the column degrees -- 10 ms of union-find on mk15.b4's factor that nothing ever read)
-		ensure_row_tables(F, stream, group_mode != 0 || (1) == 0);
+		ensure_row_tables(F, stream, group_mode != 0);
 		wide_dense = (2.0 * (double) F->prime * ((double) F->maxdeg + 3.0) >= 4294967296.0);
 	}
 	// per-wave dense scratch, (re)allocated when the factor geometry needs more
 	if (!want_bs && !want_sp) {
 		i64 slot_bytes, off_bm, off_xn;
 		wave_dense_geometry(F->rpad, F->Sm, wide_dense, &slot_bytes, &off_bm, &off_xn);
-		int slots = (cus * 32);
+		int slots = cus * 32;
 		// accumulator slices may take up to half of the free HBM (288 GB parts: be generous), or what
 		// SPASM_HIP_SCRATCH_GB says
 		size_t free_b = 0, total_b = 0;
@@ -2146,7 +2132,7 @@ int dschur_impl(const spasm_hip_dcsr *A, const int *d_rows, int nrows, const spa
 eliminated:
 	HIP_CHECK(hipEventRecord(W->ev[1], stream));
 	if (!bs_direct)
-		launch_finalize(W, nrows, sort_rows, stream);
+		launch_finalize(W, nrows, stream);
 	HIP_CHECK(hipEventRecord(W->ev[2], stream));
 
 	int ctr[CTR_COUNT];
@@ -2523,7 +2509,7 @@ static struct spasm_csr *schur_entry(const struct spasm_csr *A, const int *p, in
 	// batch go through it (under a millisecond): their entries, scaled, + 15 % + what the waves strand in their arenas
 	// (8,192 rows + 12 % still fell short once in fifteen mk14.b4 calls).
 	double ms_sample = 0.0;
-	if (L == nullptr && !shard && n >= 65536 && (1) != 0 &&
+	if (L == nullptr && !shard && n >= 65536 &&
 	    sparse_image_wanted(F, env_int("SPASM_HIP_FORCE_TIER", 0) != 0 || env_int("SPASM_HIP_GROUP", -1) >= 0, n) &&
 	    (F->sp.valid || sparse_image_build(F, stream))) {
 		const int ns = 16384;

@@ -504,7 +504,7 @@ constexpr int SORT_LDS_MAX = 8192;
 template <int CAP>
 __global__ __launch_bounds__(64) void gather_rows_kernel(const int *pool_j, const int *pool_x, const int64_t *row_off,
                                                         const int *row_len, int n, const int64_t *Sp, int *Sj, int *Sx,
-                                                        int sort_rows, int len_lo, int len_hi)
+                                                        int len_lo, int len_hi)
 {
 	__shared__ int kj[CAP];
 	__shared__ int kx[CAP];
@@ -515,9 +515,9 @@ __global__ __launch_bounds__(64) void gather_rows_kernel(const int *pool_j, cons
 			continue;
 		const int64_t raw = row_off[k];
 		const bool presorted = (raw >> 62) & 1;
-		// rows that only need copying (already sorted, or sorting is off) all belong to the first launch
+		// rows that only need copying (already sorted) all belong to the first launch
 		// (small LDS footprint, many waves); the second launch takes the long rows that must be sorted
-		const bool copy_only = !sort_rows || presorted;
+		const bool copy_only = presorted;
 		const bool mine = (len_lo == 0) ? (copy_only || len <= len_hi) : (!copy_only && len > len_lo);
 		if (!mine)
 			continue;
@@ -642,7 +642,7 @@ void launch_row_scan(const int *row_len, int n, int64_t *blocksum, int64_t *Sp, 
 	HIP_CHECK(hipGetLastError());
 }
 
-void launch_finalize(const spasm_hip_dwork *W, int nrows, int sort_rows, hipStream_t stream)
+void launch_finalize(const spasm_hip_dwork *W, int nrows, hipStream_t stream)
 {
 	const int nblocks = (nrows + 1023) / 1024;
 	if (nrows == 0) {
@@ -654,10 +654,10 @@ void launch_finalize(const spasm_hip_dwork *W, int nrows, int sort_rows, hipStre
 	hipLaunchKernelGGL(scan_finish, dim3(nblocks), dim3(256), 0, stream, W->d_row_len, nrows, W->d_blocksum, W->d_Sp);
 	int blocks = nrows < 16384 ? nrows : 16384;
 	hipLaunchKernelGGL((gather_rows_kernel<SORT_SMALL>), dim3(blocks), dim3(64), 0, stream, W->d_pool_j, W->d_pool_x,
-	                   W->d_row_off, W->d_row_len, nrows, W->d_Sp, W->d_Sj, W->d_Sx, sort_rows, 0, SORT_SMALL);
+	                   W->d_row_off, W->d_row_len, nrows, W->d_Sp, W->d_Sj, W->d_Sx, 0, SORT_SMALL);
 	blocks = nrows < 512 ? nrows : 512;
 	hipLaunchKernelGGL((gather_rows_kernel<SORT_LDS_MAX>), dim3(blocks), dim3(64), 0, stream, W->d_pool_j, W->d_pool_x,
-	                   W->d_row_off, W->d_row_len, nrows, W->d_Sp, W->d_Sj, W->d_Sx, sort_rows, SORT_SMALL, 0x7FFFFFFF);
+	                   W->d_row_off, W->d_row_len, nrows, W->d_Sp, W->d_Sj, W->d_Sx, SORT_SMALL, 0x7FFFFFFF);
 	HIP_CHECK(hipGetLastError());
 }
 

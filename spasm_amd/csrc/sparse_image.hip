@@ -57,12 +57,6 @@ constexpr uint64_t LEN_MASK = (1ull << SP_LEN_BITS) - 1;
 constexpr uint64_t OFF_MASK = (1ull << SP_OFF_BITS) - 1;
 constexpr int SHARD_STRIDE = 16;                        // 64-bit words per shard: one 128-byte line
 
-int env_sp(const char *name, int dflt)
-{
-	const char *e = sh::env_get(name);
-	return (e == nullptr || *e == 0) ? dflt : std::atoi(e);
-}
-
 template <typename T> T *dalloc(int64_t count)
 {
 	return static_cast<T *>(sh::big_alloc((size_t) (count > 0 ? count : 1) * sizeof(T)));
@@ -720,7 +714,6 @@ struct SpBuildArgs {
 	int *abort_flag;              // persistent: a wave waited too long (the grid is not resident?): everybody gives up
 	long long poll_limit;         // ... polls of one batch of dependencies before that happens
 	unsigned long long *prof;     // SPASM_HIP_SPARSE_IMAGE_PROFILE=1: 8 cycle counters (ticket, metadata, polling, adding, reservation, emit, publication)
-	int *dbg;                     // SPASM_HIP_SPARSE_IMAGE_DEBUG=1: 4 ints per workgroup (stage, task, detail, polls), read by the host's watchdog
 	SgnDev G;
 	MontDev M;                    // the 32-bit variant: coefficients in Montgomery form, values plain residues
 };
@@ -758,18 +751,6 @@ __global__ __launch_bounds__(256) void sp_reset_failed_kernel(uint64_t *frag, in
 			frag[t] = FRAG_PENDING;
 }
 
-__device__ __forceinline__ void sp_dbg(const SpBuildArgs &b, int lane, int stage, long long task, int detail)
-{
-#ifndef SP_NO_DBG
-	if (b.dbg != nullptr) {
-		int *d = b.dbg + 4 * (size_t) blockIdx.x;
-		l0_store_i32_sc1(d + 0, stage);
-		l0_store_i32_sc1(d + 1, (int) task);
-		l0_store_i32_sc1(d + 2, detail);
-	}
-#endif
-}
-
 // what a wave of the single-launch build carries from task to task: its arena in the pool, its share of the statistics
 struct SpWaveState {
 	long long ar_cur = 0, ar_end = 0;
@@ -804,8 +785,6 @@ __device__ __forceinline__ void sp_build_finish(const SpBuildArgs &b, LDS &L, in
 	uint64_t word = 0;
 	int cnt = 0;
 	if (touched) {
-		if (PERSISTENT)
-			sp_dbg(b, lane, 4, (long long) c * b.nseg + g, failed ? 1 : 0);
 		const int ub = (int) nl;          // touched columns: an upper bound of the entries (a sum that came back to zero gives none)
 		const uint32_t sh = sp_hash((uint32_t) c, (uint32_t) g);
 		unsigned long long *S = b.shard + (size_t) sh * SHARD_STRIDE;
@@ -878,7 +857,6 @@ __device__ __forceinline__ void sp_build_task(const SpBuildArgs &b, LDS &L, int 
 	const uint32_t col0 = (uint32_t) g * SP_SEG;
 	const SgnDev G = b.G;
 	const MontDev M = b.M;
-	uint64_t *fout = b.frag + (uint64_t) c * b.nseg + g;
 	unsigned long long ops = 0;
 	uint32_t nl = 0;                               // columns of the segment listed so far (sp_list_new)
 	bool touched = false, failed = false;          // (wave-uniform: they only ever change on ballots)
@@ -895,12 +873,11 @@ __device__ __forceinline__ void sp_build_task(const SpBuildArgs &b, LDS &L, int 
 		}
 	};
 	// up to 64 pivotal entries of the row (lane: compact row of the pivot, negated coefficient): minus coefficient times their fragments
-	auto dependencies = [&](bool have, uint32_t row, int coef, int detail) {
+	auto dependencies = [&](bool have, uint32_t row, int coef) {
 		uint64_t f = 0;
 		const uint64_t *fin = have ? b.frag + (uint64_t) row * b.nseg + g : b.frag;
 		st.mark(1);
 		if (PERSISTENT) {
-			sp_dbg(b, lane, 2, (long long) c * b.nseg + g, detail);
 			f = have ? __hip_atomic_load(fin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
 			long long polls = 0;
 			while (__ballot(f == FRAG_PENDING) != 0) {
@@ -925,8 +902,6 @@ __device__ __forceinline__ void sp_build_task(const SpBuildArgs &b, LDS &L, int 
 		st.mark(2);
 		if (!failed && __ballot((f & LEN_MASK) != 0) != 0) {
 			touched = true;
-			if (PERSISTENT)
-				sp_dbg(b, lane, 3, (long long) c * b.nseg + g, detail);
 			if constexpr (W32)
 				sp_accumulate<PERSISTENT>(L, f, (uint32_t) coef, true, b.pools, lane, M, ops, nl);
 			else
@@ -942,7 +917,7 @@ __device__ __forceinline__ void sp_build_task(const SpBuildArgs &b, LDS &L, int 
 		const int nd = (int) (counts & 0xFFFFu), nn = (int) (counts >> 16);
 		own_entries(lane > nd && lane <= nd + nn, hd.x, (int) hd.y);
 		if (nd > 0)
-			dependencies(lane >= 1 && lane <= nd, hd.x, (int) hd.y, 0);
+			dependencies(lane >= 1 && lane <= nd, hd.x, (int) hd.y);
 	} else {
 		const uint64_t d0 = sp_uniform(b.dep_rp[c]), d1 = sp_uniform(b.dep_rp[c + 1]), n0 = sp_uniform(b.np_rp[c]), n1 = sp_uniform(b.np_rp[c + 1]);
 		for (uint64_t e = n0; e < n1; e += 64) {
@@ -953,7 +928,7 @@ __device__ __forceinline__ void sp_build_task(const SpBuildArgs &b, LDS &L, int 
 		for (uint64_t e = d0; e < d1; e += 64) {
 			const bool have = e + lane < d1;
 			const uint2 de = have ? b.dep[e + lane] : uint2{0u, 0u};
-			dependencies(have, de.x, (int) de.y, (int) (e - d0));
+			dependencies(have, de.x, (int) de.y);
 		}
 	}
 	sp_build_finish<PERSISTENT, W32>(b, L, c, g, lane, st, ws, nl, ops, touched, failed);
@@ -992,7 +967,6 @@ __device__ __forceinline__ void sp_build_row_inline(const SpBuildArgs &b, LDS &L
 			uint32_t nl = 0;
 			bool touched = false, failed = false;
 			st.mark(1);
-			sp_dbg(b, lane, 2, (long long) c * b.nseg + g, 0);
 			long long polls = 0;
 			while (__ballot(f == FRAG_PENDING) != 0) {
 				polls += 1;
@@ -1022,7 +996,6 @@ __device__ __forceinline__ void sp_build_row_inline(const SpBuildArgs &b, LDS &L
 			}
 			if (!failed && __ballot(isdep && (f & LEN_MASK) != 0) != 0) {
 				touched = true;
-				sp_dbg(b, lane, 3, (long long) c * b.nseg + g, 0);
 				if constexpr (W32) {
 					if (have_pre)
 						sp_group_consume<true>(L, pre, f, coef, b.pools, lane, M, ops, nl);
@@ -1078,7 +1051,6 @@ template <bool PERSISTENT, bool W32 = false> __global__ __launch_bounds__(64) vo
 			const int j = l0_atomic_add_i32_ret(b.ticket + q * SP_TICKET_STRIDE, 1);
 			const long long t = (long long) j * SP_TICKETS + q;
 			st.mark(0);
-			sp_dbg(b, lane, 1, t, j);
 			if (t >= ntasks)
 				break;
 			const int c = b.row_hi - 1 - (int) t;          // rows from the last to the first
@@ -1105,9 +1077,7 @@ template <bool PERSISTENT, bool W32 = false> __global__ __launch_bounds__(64) vo
 						sp_build_task<true, W32>(b, L, c, g, lane, st, ws, hd);
 				}
 			}
-			sp_dbg(b, lane, 5, t, 0);
 		}
-		sp_dbg(b, lane, 9, 0, 0);
 		// the wave's share of the statistics (and what its last arena strands counts as reserved)
 		unsigned long long *S = b.shard + (size_t) (blockIdx.x % SP_SHARDS) * SHARD_STRIDE;
 		l0_atomic_add_u64(&S[2], ws.ops);
@@ -1617,7 +1587,7 @@ template <bool W32> __global__ __launch_bounds__(256) void sp_gather_kernel(SpGa
 // (SPASM_HIP_SPARSE_IMAGE_WIDE=1 takes the 32-bit variant for small primes too: tests)
 bool sparse_image_possible(int64_t prime)
 {
-	return prime >= 3 && prime < ((int64_t) 1 << 32) && (prime & 1) != 0 && env_sp("SPASM_HIP_SPARSE_IMAGE", -1) != 0;
+	return prime >= 3 && prime < ((int64_t) 1 << 32) && (prime & 1) != 0 && env_int("SPASM_HIP_SPARSE_IMAGE", -1) != 0;
 }
 
 // dependency tables of the build: per compact row (level order) its pivotal entries (compact row, negated balanced
@@ -1643,7 +1613,7 @@ void sparse_image_plan_sizes(const FactPlan &P, spasm_hip_dfact *F)
 	S.Sm = P.m - P.r;
 	S.nseg = (S.Sm + SP_SEG - 1) / SP_SEG;
 	S.nlevels = P.nlevels;
-	S.wide = !sgn_eligible(P.prime) || env_sp("SPASM_HIP_SPARSE_IMAGE_WIDE", 0) != 0;
+	S.wide = !sgn_eligible(P.prime) || env_int("SPASM_HIP_SPARSE_IMAGE_WIDE", 0) != 0;
 	S.lvl_lo.assign((size_t) P.nlevels + 1, 0);
 	for (int l = 0; l < P.nlevels; l++)
 		S.lvl_lo[l + 1] = S.lvl_lo[l] + P.lvl_count[l];
@@ -1809,7 +1779,7 @@ void sparse_image_plan_start(const FactPlan &P, spasm_hip_dfact *F)
 	const FactPlan *plan = &P;
 	SpPending *raw = H.get();
 	H->t_start = wtime();
-	H->worker = std::thread([plan, wide, raw]() {
+	H->worker = library_thread([plan, wide, raw]() {
 		sparse_image_plan_host(*plan, wide, *raw);
 		raw->t_done = wtime();
 	});
@@ -1905,8 +1875,8 @@ bool sparse_image_build(const spasm_hip_dfact *F, hipStream_t stream)
 	for (int k = 0; k < S.nchunks; k++)
 		held += S.chunk_cap[k] * esize;
 	int64_t budget = std::min<int64_t>((int64_t) ((free_b + (size_t) held) / 3), std::max<int64_t>((int64_t) S.r * (int64_t) S.Sm, (int64_t) 256 << 20));
-	if (env_sp("SPASM_HIP_SPARSE_IMAGE_GB", 0) > 0)
-		budget = (int64_t) env_sp("SPASM_HIP_SPARSE_IMAGE_GB", 0) << 30;
+	if (env_int("SPASM_HIP_SPARSE_IMAGE_GB", 0) > 0)
+		budget = (int64_t) env_int("SPASM_HIP_SPARSE_IMAGE_GB", 0) << 30;
 	// a rebuild of an image that needed several chunks: one chunk of the size that is known now
 	if (S.nchunks > 1 && S.pool_used > 0) {
 		sparse_image_drop_chunks(S);
@@ -1917,8 +1887,8 @@ bool sparse_image_build(const spasm_hip_dfact *F, hipStream_t stream)
 		                                 : std::max<int64_t>((int64_t) 16 << 20, std::max<int64_t>(64 * (F->nnz + S.r), (int64_t) 1536 * S.r));
 		// (first guess: the rows of R of the generated families hold 550-870 entries on average, and a segment reserves room for
 		//  every column it touched, cancelled or not; a guess that is too small costs a second launch, one too large only address space)
-		if (env_sp("SPASM_HIP_SPARSE_IMAGE_CHUNK", 0) > 0)          // (tests: pool extensions on small inputs)
-			cap = env_sp("SPASM_HIP_SPARSE_IMAGE_CHUNK", 0);
+		if (env_int("SPASM_HIP_SPARSE_IMAGE_CHUNK", 0) > 0)          // (tests: pool extensions on small inputs)
+			cap = env_int("SPASM_HIP_SPARSE_IMAGE_CHUNK", 0);
 		cap = std::min<int64_t>(cap, std::max<int64_t>(budget / esize, (int64_t) SP_SHARDS * 64));
 		cap = (cap + SP_SHARDS - 1) / SP_SHARDS * SP_SHARDS;
 		S.d_chunk[0] = dalloc<uint32_t>(cap * (esize / 4));
@@ -1939,7 +1909,7 @@ bool sparse_image_build(const spasm_hip_dfact *F, hipStream_t stream)
 	b.abort_flag = d_abort;
 	b.poll_limit = (long long) (1 << 21);
 	unsigned long long *d_prof = nullptr;
-	if (env_sp("SPASM_HIP_SPARSE_IMAGE_PROFILE", 0) != 0) {
+	if (env_int("SPASM_HIP_SPARSE_IMAGE_PROFILE", 0) != 0) {
 		d_prof = dalloc<unsigned long long>(8);
 		HIP_CHECK(hipMemsetAsync(d_prof, 0, 8 * sizeof(unsigned long long), stream));
 	}
@@ -1955,7 +1925,7 @@ bool sparse_image_build(const spasm_hip_dfact *F, hipStream_t stream)
 	else
 		HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sp_build_kernel<true, false>, 64, 0));
 	per_cu = std::min(per_cu, ((int) std::min<size_t>(32, (size_t) (160 * 1024) / (S.wide ? sizeof(WaveLds32) : sizeof(WaveLds)))));
-	bool persistent = env_sp("SPASM_HIP_SPARSE_IMAGE_PERSISTENT", 1) != 0 && per_cu >= 1;          // (0: the level-by-level fall-back, for the stress runs)
+	bool persistent = env_int("SPASM_HIP_SPARSE_IMAGE_PERSISTENT", 1) != 0 && per_cu >= 1;          // (0: the level-by-level fall-back, for the stress runs)
 	HIP_CHECK(hipEventRecord(S.ev0, stream));
 	auto next_chunk = [&](int chunk) -> bool {          // room for another attempt?  (allocates chunk + 1 when it is not there)
 		int64_t total = 0;
@@ -2003,15 +1973,9 @@ bool sparse_image_build(const spasm_hip_dfact *F, hipStream_t stream)
 		for (bool first = true;; first = false) {
 			set_chunk(chunk, first);
 			// (arenas of 16,384 entries when the chunk is large enough for every wave to strand one; tests with tiny chunks: none)
-			b.arena = (S.chunk_cap[chunk] >= (int64_t) blocks * 16384 * 4 && (1) != 0) ? 16384 : 0;
+			b.arena = (S.chunk_cap[chunk] >= (int64_t) blocks * 16384 * 4) ? 16384 : 0;
 			b.retry = first ? 0 : 1;
 			HIP_CHECK(hipMemsetAsync(d_sync, 0, (size_t) (SP_TICKETS * SP_TICKET_STRIDE + 2) * sizeof(int), stream));
-			int *d_dbg = nullptr;
-			if ((0) != 0) {
-				d_dbg = dalloc<int>((int64_t) blocks * 4);
-				HIP_CHECK(hipMemsetAsync(d_dbg, 0, (size_t) blocks * 4 * sizeof(int), stream));
-			}
-			b.dbg = d_dbg;
 			// A COOPERATIVE launch: the tasks of this kernel wait for each other, which only ends when every wave of the grid is
 			// resident -- the runtime then refuses a grid that is not (an error at launch time instead of a stall), and does not
 			// start it beside work that holds part of the chip.
@@ -2023,8 +1987,6 @@ bool sparse_image_build(const spasm_hip_dfact *F, hipStream_t stream)
 					(void) hipGetLastError();
 					logmsg("[sparse image] the single-launch build cannot be resident here (%s); building level by level\n", hipGetErrorString(le));
 					counters()[CNT_SP_BUILD_ABORTS] += 1;
-					if (d_dbg != nullptr)
-						sh::big_free(d_dbg);
 					persistent = false;
 					chunk = 0;
 					break;
@@ -2033,7 +1995,7 @@ bool sparse_image_build(const spasm_hip_dfact *F, hipStream_t stream)
 			S.launches += 1;
 			{
 				// second line of defence, a watchdog: a launch that is still running after `patience` seconds is told to give up (the abort flag, written
-				// from a stream of its own); what the ticket counters and the wave marks say goes to stderr.  The host sleeps
+				// from a stream of its own); what the ticket counters say goes to stderr.  The host sleeps
 				// between its looks at the stream.
 				// (patience grows with the factor: 5 s -- a hundred times the longest build measured, 0.05 s for 3 M dependencies -- plus
 				//  a second per million dependencies, and at least 20 s for the 32-bit variant, which runs nine waves per CU)
@@ -2051,22 +2013,6 @@ bool sparse_image_build(const spasm_hip_dfact *F, hipStream_t stream)
 					for (int q = 0; q < SP_TICKETS; q++)
 						fprintf(stderr, " %d", hs[(size_t) q * SP_TICKET_STRIDE]);
 					fprintf(stderr, "; abort %d, overflow %d\n", hs[(size_t) SP_TICKETS * SP_TICKET_STRIDE], hs[(size_t) SP_TICKETS * SP_TICKET_STRIDE + 1]);
-					if (d_dbg != nullptr) {
-						std::vector<int> hd((size_t) blocks * 4);
-						HIP_CHECK(hipMemcpyAsync(hd.data(), d_dbg, hd.size() * sizeof(int), hipMemcpyDeviceToHost, side));
-						HIP_CHECK(hipStreamSynchronize(side));
-						int hist[10] = {0};
-						for (int w = 0; w < blocks; w++)
-							hist[std::max(0, std::min(9, hd[(size_t) w * 4]))] += 1;
-						fprintf(stderr, "[sparse image/debug] waves by stage: not started %d, ticket %d, polling %d, adding %d, emit %d, task done %d, exited %d\n",
-						        hist[0], hist[1], hist[2], hist[3], hist[4], hist[5], hist[9]);
-						int shown = 0;
-						for (int w = 0; w < blocks && shown < 24; w++)
-							if (hd[(size_t) w * 4] != 9 && hd[(size_t) w * 4] != 0) {
-								fprintf(stderr, "[sparse image/debug]   wave %d: stage %d, task %d, detail %d\n", w, hd[(size_t) w * 4], hd[(size_t) w * 4 + 1], hd[(size_t) w * 4 + 2]);
-								shown += 1;
-							}
-					}
 					// a sample of the fragment words: how many are still pending?
 					{
 						const int64_t ns = std::min<int64_t>(nfrag, 1 << 20);
@@ -2092,8 +2038,6 @@ bool sparse_image_build(const spasm_hip_dfact *F, hipStream_t stream)
 			int flags[2] = {0, 0};          // abort, overflow
 			HIP_CHECK(hipMemcpyAsync(flags, d_abort, sizeof(flags), hipMemcpyDeviceToHost, stream));
 			HIP_CHECK(hipStreamSynchronize(stream));
-			if (d_dbg != nullptr)
-				sh::big_free(d_dbg);
 			if (verbose() >= 3)
 				logmsg("[sparse image] launch %d on chunk %d (%lld entries): abort %d, overflow %d\n", S.launches, chunk, (long long) S.chunk_cap[chunk], flags[0], flags[1]);
 			if (flags[0] != 0) {
@@ -2269,7 +2213,7 @@ void launch_sparse_image_apply(const SchurArgs &a, const spasm_hip_dfact *F, uin
 	HIP_CHECK(hipMemsetAsync(block_sum, 0, (size_t) nblocks * sizeof(unsigned long long), stream));
 	HIP_CHECK(hipMemsetAsync(Sp, 0, sizeof(int64_t), stream));
 	unsigned long long *d_prof = nullptr;
-	if (env_sp("SPASM_HIP_SPARSE_IMAGE_PROFILE", 0) != 0) {
+	if (env_int("SPASM_HIP_SPARSE_IMAGE_PROFILE", 0) != 0) {
 		d_prof = dalloc<unsigned long long>(8);
 		HIP_CHECK(hipMemsetAsync(d_prof, 0, 8 * sizeof(unsigned long long), stream));
 	}

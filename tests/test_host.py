@@ -31,6 +31,22 @@ def test_no_product_dependency_on_oracle():
                 assert "oracle" not in text.replace("no CPU fallback", ""), (dirpath, f)
 
 
+def test_every_named_switch_is_read():
+    """a SPASM_HIP_* name in the library's sources or headers is a switch the code reads, or one of the few that are not switches."""
+    texts = []
+    for d in (os.path.join(ROOT, "spasm_amd", "csrc"), os.path.join(ROOT, "include")):
+        for f in sorted(os.listdir(d)):
+            if f.endswith((".hip", ".cpp", ".h", ".c")) or f == "Makefile":
+                texts.append(open(os.path.join(d, f)).read())
+    text = "\n".join(texts)
+    read = set(re.findall(r"\b(?:env_get|env_int|getenv)\(\s*\"(SPASM_HIP_[A-Z0-9_]+)\"", text))
+    assert {"SPASM_HIP_VERBOSE", "SPASM_HIP_BS_SHAPE", "SPASM_HIP_SPARSE_IMAGE_PROFILE"} <= read
+    names = set(re.findall(r"\bSPASM_HIP_[A-Z0-9_]+", text))
+    not_switches = {"SPASM_HIP_H", "SPASM_HIP_SHIM_H", "SPASM_HIP_LIB"}
+    stale = sorted(n for n in names - read - not_switches if not n.startswith("SPASM_HIP_XFER_"))
+    assert not stale, stale
+
+
 def test_compute_entry_points_fail_loudly_without_gpu(oracle):
     if spasm_amd.device_count() > 0:
         pytest.skip("a GPU is present")
