@@ -8,8 +8,14 @@ structural pivots found on the host, then ONE STEP = the Schur complement of eve
 those pivots (spasm_schur, spasm_schur.c:61) -- here spasm_hip_dschur with A, the factor image and the row
 list already resident in HBM.  Derived factor state (the back-substituted rows R = U_pp^-1 U_pn) is
 forgotten before every step, so a step pays for all of spasm_schur.  There is no network: the matrix is
-regenerated from its definition (tools/workloads.py) unless $SPASM_DATA/mk13.b5.sms exists; `data` says which.
-The other BASELINE configs are data files; `configs` in the output says which are present.
+regenerated from its definition (tools/workloads.py) unless $SPASM_DATA/mk13.b5.sms exists; `data` says which, and
+the pivots are searched again in every run (nothing an earlier run left on disk is read).
+The other BASELINE configs are data files; with --full, `configs` in the output says which are present.
+
+A plain run does only what the headline needs: set up, warm up, time the steps, dump the last one's S if asked, print the
+line (its `roofline` comes from the timed steps' own counters).  Everything else below -- the factor image's build time, the
+other paths and sizes, the end-to-end calls, the CPU baselines, the device-API step next to the product's at N > 1 -- is
+measured only with --full.
 
 Prints ONE JSON line (rank 0).  N > 1 (launched by torch.distributed.run), strong scaling (the matrix is fixed), two
 splits (--split): `columns` -- the default when the factor takes the back-substituted path, whose columns never meet --
@@ -23,7 +29,7 @@ passes: it is quoted from profiles/r06_traffic.json (written by tools/profile.sh
 next) only when that file was recorded for the same kernel on the same workload, with its path in
 `traffic_source`; otherwise null.
 
-Next to the step, on one GPU: the same batch through the row-by-row kernels, the dense tail, five end-to-end calls
+With --full, next to the step, on one GPU: the same batch through the row-by-row kernels, the dense tail, five end-to-end calls
 (first call, median and minimum are all reported), `sparse_path` -- the flow of the GL7d19 class on the generated
 stand-in mk14.b4: its Schur complement through the sparse image (the default there), the dense image and the
 row-by-row kernels --, `at_scale` -- mk15.b4, 2,837,835 x 675,675 with 14.2 M entries, the size of GL7d19 -- and the
@@ -352,7 +358,7 @@ def sparse_path_probe(torch, spasm_amd, workloads, dev, name="mk14.b4", steps=3,
     the SPARSE image: R = U_pp^-1 U_pn as sparse fragments, sparse_image.hip -- and, where they exist for the factor, through
     the dense image and the row-by-row kernels; then whole spasm_hip_echelonize calls with their time split."""
     t0 = time.perf_counter()
-    A, rows, F, source = workloads.round0(name, PRIME, threads=0)
+    A, rows, F, source = workloads.round0(name, PRIME, cache=False, threads=0)
     t_prep = time.perf_counter() - t0
     dA = spasm_amd.DeviceCsr.from_host(A, dev)
     drows = torch.from_numpy(np.ascontiguousarray(rows)).to(dev)
@@ -450,7 +456,7 @@ def sparse_path_probe(torch, spasm_amd, workloads, dev, name="mk14.b4", steps=3,
     # the same step on a pivot set that does not depend on timing (the sequential search with depth labels, one thread): the
     # device search above finds a different set in every run, and with it a Schur complement of another size
     t0 = time.perf_counter()
-    A1, rows1, F1, _ = workloads.round0(name, PRIME, threads=1, labelled=True)
+    A1, rows1, F1, _ = workloads.round0(name, PRIME, cache=False, threads=1, labelled=True)
     t_fixed = time.perf_counter() - t0
     rows_keep, F_keep = rows, F
     try:
@@ -575,18 +581,24 @@ def main():
                          "an all-gatherv over RCCL; `columns` = every rank owns a slab of the non-pivotal columns of ALL rows "
                          "(spasm_hip_column_slab: no replicated factor image, only the row lengths are exchanged); auto = columns "
                          "(the columns of R and S never meet on either image path)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline step: the factor image's build time, the row-by-row comparison, the "
+                         "dense-tail probes, the end-to-end calls, the stand-ins at other sizes, the CPU baselines, the BASELINE configs "
+                         "present; at N > 1 the device-API step of the same split next to the product's")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--beyond-scale", action="store_true",
-                    help="also run spasm_hip_echelonize twice on mk15.b5 (4,729,725 x 2,837,835, 28.4 M entries: beyond the size of GL7d19; "
-                         "about a minute more, 40 GB of device memory) and report it as `beyond_scale`")
+                    help="with --full: also run spasm_hip_echelonize twice on mk15.b5 (4,729,725 x 2,837,835, 28.4 M entries: beyond the "
+                         "size of GL7d19; about a minute more, 40 GB of device memory) and report it as `beyond_scale`")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the row-by-row comparison, the dense-tail probe and the end-to-end runs")
+                    help="with --full: skip the row-by-row comparison, the dense-tail probes, the end-to-end calls and the stand-ins")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last one computed (the Schur complement: all row pointers, the entries "
                          "of a fixed seeded sample of rows) as DIR/<name>.npy, float32/float64, at most 64 MB in all; one process only")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.beyond_scale and not args.full:
+        ap.error("--beyond-scale: only with --full")
     if args.dump_outputs and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("SPASM_BENCH_FORCE_DIST") == "1"):
         ap.error("--dump-outputs: one process on one GPU only")
 
@@ -650,7 +662,7 @@ def main():
         comm = Comm(rank, world, exchange)
 
     try:
-        A, rows, F, source = workloads.round0(args.workload, PRIME)
+        A, rows, F, source = workloads.round0(args.workload, PRIME, cache=False)
     except FileNotFoundError as e:
         if rank == 0:
             emit({"metric": "rows eliminated/sec (sparse Schur complement, mod 42013)", "value": None,
@@ -674,15 +686,16 @@ def main():
         my_rows = shard_rows(rows, rank, world)
     dA = spasm_amd.DeviceCsr.from_host(A, dev)
     # the factor image (host: level schedule, pass tables, chunk plans; then the upload) is built once per factor, outside
-    # the timed steps: its cost is measured here and reported next to the step (`factor_image_ms`, `rows_per_s_cold`)
+    # the timed steps; with --full its cost is measured here and reported next to the step (`factor_image_ms`, `rows_per_s_cold`)
     image_ms = []
-    for k in range(4):                           # (the first build also loads the code object and fills the buffer cache: not counted)
+    builds = 4 if args.full else 1
+    for k in range(builds):                      # (the first build also loads the code object and fills the buffer cache: not counted)
         t0 = time.perf_counter()
         dF = spasm_amd.DeviceFact(F)
         torch.cuda.synchronize()
         if k > 0:
             image_ms.append(1e3 * (time.perf_counter() - t0))
-        if k < 3:
+        if k < builds - 1:
             dF.close()
     drows = torch.from_numpy(np.ascontiguousarray(my_rows)).to(dev)
     stream = torch.cuda.Stream(device=dev)
@@ -797,16 +810,19 @@ def main():
         for _ in range(args.warmup):
             product_step()
         elapsed, _ = timed(lambda: [product_step() for _ in range(args.steps)])
-        # the device-API step, for the kernels' own times (the product's call does not hand out its stage timers) and as the
-        # second object: no gather of S, no stitching
-        for _ in range(min(args.warmup, 2)):
-            step()
-        n_slab = max(3, min(5, args.steps))
-        el_slab, (_, ms_sum, bytes_of, st) = timed(lambda: run_steps(n_slab))
-        kernel_steps = n_slab
-        slab_only = {"what": "device-API step of the same split: every rank its slab (or slice) through spasm_hip_dschur, %s -- what the product's "
-                             "step adds is the all-gatherv of S and the stitching" % ("row lengths all-gathered" if split == "columns" else "all-gatherv of S"),
-                     "steps": n_slab, "ms_per_step": 1e3 * el_slab / n_slab, "rows_per_s": len(rows) / (el_slab / n_slab)}
+        # (without --full: the kernel path and the dtype from the probing run, no kernel times -- no roofline)
+        ms_sum, bytes_of, kernel_steps = {}, {}, 1
+        if args.full:
+            # the device-API step, for the kernels' own times (the product's call does not hand out its stage timers) and as the
+            # second object: no gather of S, no stitching
+            for _ in range(min(args.warmup, 2)):
+                step()
+            n_slab = max(3, min(5, args.steps))
+            el_slab, (_, ms_sum, bytes_of, st) = timed(lambda: run_steps(n_slab))
+            kernel_steps = n_slab
+            slab_only = {"what": "device-API step of the same split: every rank its slab (or slice) through spasm_hip_dschur, %s -- what the product's "
+                                 "step adds is the all-gatherv of S and the stitching" % ("row lengths all-gathered" if split == "columns" else "all-gatherv of S"),
+                         "steps": n_slab, "ms_per_step": 1e3 * el_slab / n_slab, "rows_per_s": len(rows) / (el_slab / n_slab)}
     else:
         for _ in range(args.warmup):
             step()
@@ -818,11 +834,11 @@ def main():
         dumped = dump_outputs(torch, spasm_amd, W, st, len(my_rows), A.m, stream, args.dump_outputs)
 
     total_nnz_all = int(st.nnz)
-    if use_dist and split == "columns":
+    if slab_only is not None and split == "columns":
         total_nnz_all = int(all_len.sum().item())          # entries of the whole Schur complement, from the exchanged lengths
-    if product is not None:
-        if total_nnz_all != product_nnz[0] and split == "columns":
+        if total_nnz_all != product_nnz[0]:
             raise SystemExit("bench.py: the product's Schur complement holds %d entries, the slabs %d" % (product_nnz[0], total_nnz_all))
+    if product is not None:
         total_nnz_all = product_nnz[0]
     if rank == 0:
         total_rows = len(rows)
@@ -834,51 +850,53 @@ def main():
                 continue
             kernels[name] = {"ms": k_ms, "algorithmic_bytes": int(bytes_of[name]),
                              "GB_per_s": bytes_of[name] / (k_ms * 1e-3) / 1e9}
-        dom_name = max(kernels, key=lambda k: kernels[k]["ms"])
-        dom = kernels[dom_name]
-        kernel_id = dom_name.split(" ")[0]
-        traffic, traffic_hi, traffic_src = (None, None, None)
-        if world == 1:
-            traffic, traffic_hi, traffic_src = quoted_traffic(kernel_id, args.workload, total_rows)
-        if world == 1:          # HBM bytes of the other kernels of the step, from the same counter passes
-            for kname, kd in kernels.items():
-                tr = quoted_traffic(kname.split(" ")[0], args.workload, total_rows)
-                if tr[0]:
-                    kd["traffic"] = tr[0]
-                    kd["hbm_frac"] = tr[0] / (kd["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
-        step_bytes = sum(k["algorithmic_bytes"] for k in kernels.values())
-        roof = {"bound": "hbm", "achieved": dom["GB_per_s"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": dom["GB_per_s"] / HBM_PEAK_GBS, "traffic": traffic,
-                "kernel": kernel_id, "kernel_ms": dom["ms"], "algorithmic_bytes": dom["algorithmic_bytes"],
-                "what_frac_is": "algorithmic bytes of this kernel (DESIGN.md section 4) / its device time / 8 TB/s",
-                "hbm_frac": (traffic / (dom["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
-                "hbm_frac_fetch_doubled": (traffic_hi / (dom["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic_hi else None,
-                "traffic_source": traffic_src,
-                "kernels": kernels,
-                "step_algorithmic_bytes": int(step_bytes),
-                "step_GB_per_s": step_bytes / (ms_per_step * 1e-3) / 1e9,
-                "step_frac": step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS}
-        # The dense image's build is not bound by bytes: its workgroups -- one per slab of columns, 207 on mk13.b5 -- are bound
-        # by what ONE compute unit issues.  From the SQ counters of profiles/r06_backsolve_sq.json (tools/profile_backsolve_sq.sh), when
-        # they were recorded for this kernel: the time the vector instructions alone need on the compute units the kernel occupies.
-        sq_path = os.path.join(ROOT, "profiles", "r06_backsolve_sq.json")
-        if st.used_backsolve and os.path.exists(sq_path):
-            try:
-                sq = json.load(open(sq_path))["kernels"]
-                key = [k for k in sq if k.replace(" ", "") == kernel_id.replace(" ", "")]
-                if key:
-                    pl = sq[key[0]]["per_launch"]
-                    words = (int(A_full.m - F_full.U.n) + 1) // 2
-                    wgs = min(256, (words + 11) // 12)
-                    valu_ms = 1e3 * pl["SQ_INSTS_VALU"] * 4.0 / (wgs * 4) / 2.4e9          # a wave64 vector instruction holds its SIMD for four cycles
-                    roof["issue_bound"] = {"what": "vector instructions of the kernel x 4 cycles / (4 SIMDs x the %d compute units its %d workgroups occupy) / 2.4 GHz" % (wgs, wgs),
-                                           "valu_wave_instructions": pl["SQ_INSTS_VALU"], "lds_wave_instructions": pl.get("SQ_INSTS_LDS"), "compute_units_used": wgs,
-                                           "valu_bound_ms": valu_ms, "frac_of_valu_bound": valu_ms / dom["ms"], "source": "profiles/r06_backsolve_sq.json"}
-            except (ValueError, KeyError):
-                pass
-        if st.used_backsolve and st.bytes_staged > 0:
-            roof["staged_bytes"] = int(st.bytes_staged)
-            roof["staged_bytes_note"] = "packed rows of S between the apply and the expansion kernels: written once, read once; not algorithmic bytes"
+        roof = None          # (no kernel times: several GPUs without --full)
+        if kernels:
+            dom_name = max(kernels, key=lambda k: kernels[k]["ms"])
+            dom = kernels[dom_name]
+            kernel_id = dom_name.split(" ")[0]
+            traffic, traffic_hi, traffic_src = (None, None, None)
+            if world == 1:
+                traffic, traffic_hi, traffic_src = quoted_traffic(kernel_id, args.workload, total_rows)
+            if world == 1:          # HBM bytes of the other kernels of the step, from the same counter passes
+                for kname, kd in kernels.items():
+                    tr = quoted_traffic(kname.split(" ")[0], args.workload, total_rows)
+                    if tr[0]:
+                        kd["traffic"] = tr[0]
+                        kd["hbm_frac"] = tr[0] / (kd["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS
+            step_bytes = sum(k["algorithmic_bytes"] for k in kernels.values())
+            roof = {"bound": "hbm", "achieved": dom["GB_per_s"], "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": dom["GB_per_s"] / HBM_PEAK_GBS, "traffic": traffic,
+                    "kernel": kernel_id, "kernel_ms": dom["ms"], "algorithmic_bytes": dom["algorithmic_bytes"],
+                    "what_frac_is": "algorithmic bytes of this kernel (DESIGN.md section 4) / its device time / 8 TB/s",
+                    "hbm_frac": (traffic / (dom["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic else None,
+                    "hbm_frac_fetch_doubled": (traffic_hi / (dom["ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS) if traffic_hi else None,
+                    "traffic_source": traffic_src,
+                    "kernels": kernels,
+                    "step_algorithmic_bytes": int(step_bytes),
+                    "step_GB_per_s": step_bytes / (ms_per_step * 1e-3) / 1e9,
+                    "step_frac": step_bytes / (ms_per_step * 1e-3) / 1e9 / HBM_PEAK_GBS}
+            # The dense image's build is not bound by bytes: its workgroups -- one per slab of columns, 207 on mk13.b5 -- are bound
+            # by what ONE compute unit issues.  From the SQ counters of profiles/r06_backsolve_sq.json (tools/profile_backsolve_sq.sh), when
+            # they were recorded for this kernel: the time the vector instructions alone need on the compute units the kernel occupies.
+            sq_path = os.path.join(ROOT, "profiles", "r06_backsolve_sq.json")
+            if st.used_backsolve and os.path.exists(sq_path):
+                try:
+                    sq = json.load(open(sq_path))["kernels"]
+                    key = [k for k in sq if k.replace(" ", "") == kernel_id.replace(" ", "")]
+                    if key:
+                        pl = sq[key[0]]["per_launch"]
+                        words = (int(A_full.m - F_full.U.n) + 1) // 2
+                        wgs = min(256, (words + 11) // 12)
+                        valu_ms = 1e3 * pl["SQ_INSTS_VALU"] * 4.0 / (wgs * 4) / 2.4e9          # a wave64 vector instruction holds its SIMD for four cycles
+                        roof["issue_bound"] = {"what": "vector instructions of the kernel x 4 cycles / (4 SIMDs x the %d compute units its %d workgroups occupy) / 2.4 GHz" % (wgs, wgs),
+                                               "valu_wave_instructions": pl["SQ_INSTS_VALU"], "lds_wave_instructions": pl.get("SQ_INSTS_LDS"), "compute_units_used": wgs,
+                                               "valu_bound_ms": valu_ms, "frac_of_valu_bound": valu_ms / dom["ms"], "source": "profiles/r06_backsolve_sq.json"}
+                except (ValueError, KeyError):
+                    pass
+            if st.used_backsolve and st.bytes_staged > 0:
+                roof["staged_bytes"] = int(st.bytes_staged)
+                roof["staged_bytes_note"] = "packed rows of S between the apply and the expansion kernels: written once, read once; not algorithmic bytes"
 
         out = {
             "metric": "rows eliminated/sec (sparse Schur complement, mod 42013)",
@@ -904,22 +922,26 @@ def main():
                        "sharding": ("spasm_hip_schur with the communicator installed (%d rank(s)): slabs of the non-pivotal columns (%d of %d here), "
                                     "all-gatherv of S (%d entries) + stitching in the step" % (world, A.m - F.U.n, A_full.m - F_full.U.n, total_nnz_all)) if (split == "columns" and product is not None)
                        else "rows over %d rank(s)%s" % (world, ", spasm_hip_schur with the communicator installed: all-gatherv of S in the step" if product is not None else "")},
-            "roofline": roof,
-            "factor_image_ms": statistics.median(image_ms),
-            "factor_image_ms_all": image_ms,
-            "factor_image_note": "host planning + upload of the factor image (spasm_hip_dfact_create), once per factor, NOT in a step; "
-                                 "median of 3 builds after a first one that is not counted (it loads the code object and fills the buffer cache)",
-            "rows_per_s_cold": total_rows / (elapsed / args.steps + 1e-3 * statistics.median(image_ms)),
         }
+        if roof is not None:
+            out["roofline"] = roof
+        if image_ms:
+            out.update({
+                "factor_image_ms": statistics.median(image_ms),
+                "factor_image_ms_all": image_ms,
+                "factor_image_note": "host planning + upload of the factor image (spasm_hip_dfact_create), once per factor, NOT in a step; "
+                                     "median of 3 builds after a first one that is not counted (it loads the code object and fills the buffer cache)",
+                "rows_per_s_cold": total_rows / (elapsed / args.steps + 1e-3 * statistics.median(image_ms))})
         if dumped is not None:
             out["outputs_dumped"] = {"dir": args.dump_outputs, "files": dumped}
-        if slab_only is not None:
+        if product is not None:
             out["dist_product_path"] = {"what": "value / ms_per_step: spasm_hip_schur_resident = spasm_hip_schur as the driver calls it, communicator installed "
-                                                "(slab or slice, all-gatherv of S, stitching); roofline.kernels: measured in the slab_only steps",
-                                        "ms_per_step": ms_per_step, "slab_only_ms_per_step": slab_only["ms_per_step"], "slab_only_rows_per_s": slab_only["rows_per_s"],
-                                        "schur_nnz": total_nnz_all, "split": split}
+                                                "(slab or slice, all-gatherv of S, stitching); roofline.kernels: measured in the slab_only steps (--full)",
+                                        "ms_per_step": ms_per_step, "schur_nnz": total_nnz_all, "split": split}
+        if slab_only is not None:
+            out["dist_product_path"].update({"slab_only_ms_per_step": slab_only["ms_per_step"], "slab_only_rows_per_s": slab_only["rows_per_s"]})
             out["slab_only"] = slab_only
-        extras = world == 1 and not args.no_extras and product is None
+        extras = args.full and world == 1 and not args.no_extras and product is None
         if extras and st.used_backsolve:
             # the same batch through the row-by-row elimination kernels (what round 1 measured), a few steps
             os.environ["SPASM_HIP_BACKSOLVE"] = "0"
@@ -996,11 +1018,12 @@ def main():
             out["beyond_scale"] = dict(_calls(call_big, 2), what="spasm_hip_echelonize on mk15.b5 (%d x %d, %d entries: generated, beyond the size of GL7d19), defaults, 2 calls"
                                                                    % (Abig.n, Abig.m, Abig.nnz))
             del Abig
-        out["configs"] = [{"name": c["name"], "status": status, "what": c["what"],
-                           "bench": "python bench.py --workload %s" % c["name"],
-                           "rank": "./tools/rank --matrix $SPASM_DATA/%s --modulus %d %s" % (c["file"], PRIME, " ".join(c["rank_args"]))}
-                          for c, status, _ in workloads.discover()]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out["configs"] = [{"name": c["name"], "status": status, "what": c["what"],
+                               "bench": "python bench.py --workload %s" % c["name"],
+                               "rank": "./tools/rank --matrix $SPASM_DATA/%s --modulus %d %s" % (c["file"], PRIME, " ".join(c["rank_args"]))}
+                              for c, status, _ in workloads.discover()]
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(A_full, rows, F_full)
             rt = cpu_rank_time(A_full)
             if rt:

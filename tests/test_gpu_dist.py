@@ -127,7 +127,7 @@ def test_bench_runs_its_rccl_path_on_one_gpu():
     env = dict(os.environ, SPASM_BENCH_FORCE_DIST="1", SPASM_HIP_VERBOSE="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29871",
                RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "mk11.b4", "--steps", "2", "--warmup", "1",
-                          "--no-extras", "--no-cpu-baseline", "--split", "rows"], capture_output=True, text=True, env=env, timeout=600)
+                          "--full", "--no-extras", "--no-cpu-baseline", "--split", "rows"], capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     import json
     assert len([x for x in out.stdout.splitlines() if x.strip()]) == 1, out.stdout[:2000]          # one line, the last thing on stdout
@@ -144,7 +144,7 @@ def test_bench_runs_its_column_split_on_one_gpu():
     env = dict(os.environ, SPASM_BENCH_FORCE_DIST="1", SPASM_HIP_VERBOSE="0", MASTER_ADDR="127.0.0.1", MASTER_PORT="29873",
                RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "mk11.b4", "--steps", "2", "--warmup", "1",
-                          "--no-extras", "--no-cpu-baseline", "--split", "columns"], capture_output=True, text=True, env=env, timeout=600)
+                          "--full", "--no-extras", "--no-cpu-baseline", "--split", "columns"], capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     import json
     d = json.loads(out.stdout.strip().splitlines()[-1])

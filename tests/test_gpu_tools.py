@@ -130,3 +130,27 @@ def test_reference_kernel_c_linked_against_the_facade(oracle):
     lines = out.stdout.strip().split("\n")
     kn, km, _ = lines[0].split()
     assert int(kn) > 0
+
+
+def test_plain_bench_run_measures_only_its_headline(tmp_path):
+    """bench.py without --full: the timed steps and their line (roofline from the steps' own counters), the dumped S, and
+    none of what --full adds (factor image rebuilds, other paths and sizes, end-to-end calls, CPU baselines, configs)."""
+    import json
+    import sys
+    env = dict(os.environ, SPASM_HIP_VERBOSE="0")
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "mk11.b4", "--steps", "2", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, env=env, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [x for x in out.stdout.splitlines() if x.strip()]
+    assert len(lines) == 1, out.stdout[:2000]
+    d = json.loads(lines[-1])
+    assert d["value"] > 0 and d["ms_per_step"] > 0 and d["unit"] == "rows/s" and d["higher_is_better"] is True and d["dtype"]
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["config"]["schur_nnz"] > 0
+    assert d["roofline"]["kernels"] and d["roofline"]["frac"] > 0
+    for key in ("cpu_baseline", "factor_image_ms", "rows_per_s_cold"):
+        assert key not in d, key
+    assert d["summary"] == {}
+    assert sorted(os.listdir(str(tmp_path))) == sorted(["S_row_pointers.npy", "S_sample_rows.npy", "S_sample_row_pointers.npy",
+                                                        "S_sample_columns.npy", "S_sample_values.npy"])
+    p = np.load(os.path.join(str(tmp_path), "S_row_pointers.npy"))
+    assert int(p[-1]) == d["config"]["schur_nnz"]

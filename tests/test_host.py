@@ -506,6 +506,18 @@ def test_bench_line_is_compact_and_carries_roofline_and_cpu_baseline():
     assert err["value"] is None and err["error"] == "no such file"
 
 
+def test_bench_takes_the_larger_sizes_only_with_full():
+    """--full switches on everything besides the headline step; --beyond-scale is a part of it and is refused without it
+    (before anything touches a GPU)"""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--beyond-scale"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "only with --full" in r.stderr and not r.stdout.strip()
+
+
 def test_bench_prints_its_line_last_on_stdout_and_nothing_else(tmp_path):
     """bench.py sends everything else that reaches descriptor 1 to stderr: run its emit path in a child process whose C library
     also writes to stdout, and look at what the pipe holds"""
