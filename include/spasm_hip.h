@@ -128,6 +128,16 @@ struct spasm_rank_certificate {        /* spasm.h:110-118 */
 	spasm_ZZp *y;                      /* size r */
 };
 
+struct spasm_dm {                      /* spasm.h:74-82: a Dulmage-Mendelsohn decomposition */
+	int *p;                        /* size n, row permutation */
+	int *q;                        /* size m, column permutation */
+	int *r;                        /* size nb + 1: block k is rows r[k] .. r[k+1]-1 of A(p, q) (room for n + 6) */
+	int *c;                        /* size nb + 1: block k is columns c[k] .. c[k+1]-1 (room for m + 6) */
+	int nb;                        /* number of blocks of the fine decomposition */
+	int rr[5];                     /* coarse row decomposition */
+	int cc[5];                     /* coarse column decomposition */
+};
+
 typedef enum {SPASM_DOUBLE, SPASM_FLOAT, SPASM_I64} spasm_datatype;   /* spasm.h:139 */
 #endif /* _SPASM_H */
 
@@ -303,6 +313,35 @@ void spasm_hip_rank_certificate_save(const struct spasm_rank_certificate *proof,
 bool spasm_hip_rank_certificate_load(FILE *f, struct spasm_rank_certificate *proof);                   /* spasm_certificate.c:242 */
 /* frees the four lists and the struct (what spasm_hip_certificate_rank_create returns) */
 void spasm_hip_rank_certificate_free(struct spasm_rank_certificate *proof);
+
+/* --- maximum matching and the Dulmage-Mendelsohn decomposition (replace spasm_matching.c:103, spasm_dm.c:90, spasm_scc.c:14,
+ * spasm_permutation.c:49-99; spasm_amd/csrc/matching.hip, host_dm.cpp) ---
+ * The matching runs on the device: greedy rounds, then level-synchronous augmenting phases from all free vertices of the smaller
+ * side; the two alternating searches of the coarse decomposition too.  The strongly connected components are host code.  Every
+ * result is deterministic: two calls on the same input return the same arrays.  A struct spasm_dm is malloc'ed with the field
+ * sizes of spasm_dm_alloc, so that the reference's spasm_dm_free releases one of ours and spasm_hip_dm_free one of its. */
+struct spasm_dm *spasm_hip_dm_alloc(int n, int m);                                        /* spasm_util.c:184 */
+void spasm_hip_dm_free(struct spasm_dm *P);                                               /* spasm_util.c:199 */
+/* any maximum matching (it may differ from the reference's): jmatch[i] the column of row i, imatch[j] the row of column j, or
+ * -1; returns its size.  No progress line per row. */
+int spasm_hip_maximum_matching(const struct spasm_csr *A, int *jmatch, int *imatch);      /* spasm_matching.c:103 */
+/* the size of a maximum matching (declared by the reference, spasm.h:242, never defined there) */
+int spasm_hip_structural_rank(const struct spasm_csr *A);
+/* the reference's layout: q = C0 | C1 | C2 | C3, p = R1 | R2 | R3 | R0, rr / cc their boundaries, p[t] matched to q[cc[1] + t]
+ * for t < rr[3]; fine blocks: 0 is H (rows [0, rr[1]), columns [0, cc[2])), 1 .. nb - 2 the strongly connected components of
+ * S in block upper triangular order, nb - 1 is V.  Departure: when S is empty nb = 2 (the reference returns nb = 0 and leaves
+ * its workspace in r and c, spasm_dm.c:143-144). */
+struct spasm_dm *spasm_hip_dulmage_mendelsohn(const struct spasm_csr *A);                 /* spasm_dm.c:90 */
+/* square A: p == q, r == c, A(p, p) block upper triangular with every block strongly connected (host: an iterative Tarjan) */
+struct spasm_dm *spasm_hip_strongly_connected_components(const struct spasm_csr *A);      /* spasm_scc.c:14 */
+int *spasm_hip_pinv(const int *p, int n);                                                 /* spasm_permutation.c:49 */
+/* C = A(p, qinv^-1): row i of C is row p[i] of A, column j of A is column qinv[j] of C (NULL: identity) */
+struct spasm_csr *spasm_hip_permute(const struct spasm_csr *A, const int *p, const int *qinv, int with_values);  /* :68 */
+/* the last matching / decomposition call: ms of [0] A up and its column-major pattern, [1] the greedy rounds, [2] the augmenting
+ * phases, [3] the two coarse searches and the download, [4] the coarse sets collected on the host, [5] the strongly connected
+ * components of S (host), [6] the whole call; [7] greedy size, [8] phases, [9] BFS levels, [10] ... of them inside one
+ * workgroup, [11] matching size, [12] nb.  Returns how many there are (13). */
+int spasm_hip_dm_stats(double *out, int count);
 
 /* ======================================================================
  * (D) device-resident entry points

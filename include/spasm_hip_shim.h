@@ -46,6 +46,17 @@
 #define spasm_rank_certificate_save   spasm_hip_rank_certificate_save
 #define spasm_rank_certificate_load   spasm_hip_rank_certificate_load
 
+/* matching, Dulmage-Mendelsohn, strongly connected components, permutations (spasm_matching.c, spasm_dm.c, spasm_scc.c,
+ * spasm_permutation.c, spasm_util.c) */
+#define spasm_maximum_matching        spasm_hip_maximum_matching
+#define spasm_structural_rank         spasm_hip_structural_rank
+#define spasm_dulmage_mendelsohn      spasm_hip_dulmage_mendelsohn
+#define spasm_strongly_connected_components spasm_hip_strongly_connected_components
+#define spasm_dm_alloc                spasm_hip_dm_alloc
+#define spasm_dm_free                 spasm_hip_dm_free
+#define spasm_pinv                    spasm_hip_pinv
+#define spasm_permute                 spasm_hip_permute
+
 /* containers, field, I/O (spasm_util.c, spasm_ZZp.c, spasm_triplet.c, spasm_transpose.c, spasm_io.c) */
 #define spasm_malloc                  spasm_hip_malloc
 #define spasm_calloc                  spasm_hip_calloc

@@ -11,5 +11,6 @@ from ._lib import lib, device_count, usable_cpus, release_cached_memory, LIB_PAT
 from .host import (load, compress, transpose, pivots_extract_structural, schur, ResidentSchur,       # noqa: F401
                    empty_fact, schur_dense, ffpack_rref, ffpack_LU, echelonize, echelonize_profile, echelonize_counters, rref, kernel,
                    default_opts, gesv, solve, Solver,
-                   xApy, xApy_stats, Certificate, certificate_rank_create, certificate_rank_verify, factorization_verify)
+                   xApy, xApy_stats, Certificate, certificate_rank_create, certificate_rank_verify, factorization_verify,
+                   DM, maximum_matching, structural_rank, dulmage_mendelsohn, strongly_connected_components, permute, dm_stats)
 from .device import DeviceCsr, DeviceFact, SchurWorkspace, dschur                    # noqa: F401

@@ -2,7 +2,7 @@
 import ctypes as C
 import os
 
-from .matrix import CCsr, CTriplet, CLu, EchelonizeOpts, CDcsr, CSchurStats, CField, CCertificate
+from .matrix import CCsr, CTriplet, CLu, EchelonizeOpts, CDcsr, CSchurStats, CField, CCertificate, CDm
 
 # SPASM_HIP_LIB: load another build of the same library (A/B runs of a kernel variant)
 LIB_PATH = os.environ.get("SPASM_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libspasm_hip.so")
@@ -109,6 +109,15 @@ def lib():
         "spasm_hip_rank_certificate_save": (None, [C.POINTER(CCertificate), vp]),
         "spasm_hip_rank_certificate_load": (C.c_bool, [vp, C.POINTER(CCertificate)]),
         "spasm_hip_rank_certificate_free": (None, [C.POINTER(CCertificate)]),
+        "spasm_hip_dm_alloc": (C.POINTER(CDm), [ci, ci]),
+        "spasm_hip_dm_free": (None, [C.POINTER(CDm)]),
+        "spasm_hip_maximum_matching": (ci, [pcsr, pint, pint]),
+        "spasm_hip_structural_rank": (ci, [pcsr]),
+        "spasm_hip_dulmage_mendelsohn": (C.POINTER(CDm), [pcsr]),
+        "spasm_hip_strongly_connected_components": (C.POINTER(CDm), [pcsr]),
+        "spasm_hip_pinv": (pint, [pint, ci]),
+        "spasm_hip_permute": (pcsr, [pcsr, pint, pint, ci]),
+        "spasm_hip_dm_stats": (ci, [C.POINTER(C.c_double), ci]),
         "spasm_hip_debug_prng": (None, [i64, C.c_uint64, C.c_uint32, ci, C.POINTER(C.c_int32)]),
         "spasm_hip_debug_prng_hash": (None, [C.POINTER(C.c_uint8), i64, C.c_uint32, ci, C.POINTER(C.c_int32)]),
     }

@@ -2,9 +2,15 @@
  * libspasm_hip_facade.so -- the hot path under the reference's OWN symbol names.
  *
  * An unmodified object file of cbouilla/spasm (tools/rank.o, tools/kernel.o, ...) that is linked against this
- * library before the reference's libspasm gets spasm_echelonize, spasm_schur*, spasm_ffpack_*, spasm_rref and
- * spasm_kernel and spasm_gesv from the GPU; everything else (certificates, Dulmage-Mendelsohn, I/O, ...) stays the
+ * library before the reference's libspasm gets spasm_echelonize, spasm_schur*, spasm_ffpack_*, spasm_rref, spasm_kernel,
+ * spasm_gesv, spasm_maximum_matching, spasm_structural_rank, spasm_dulmage_mendelsohn and
+ * spasm_strongly_connected_components from this library; everything else (certificates, permutations, I/O, ...) stays the
  * reference's.  Signatures: src/spasm.h (cited per function in include/spasm_hip.h).
+ *
+ * The structural functions are exported although none of the programs linked through the facade today (tools/rank.c,
+ * kernel.c, common.c) calls them: the reference's own spasm_dulmage_mendelsohn calls the other two from inside its library,
+ * which this library then reroutes, and both give the same contract (any maximum matching; a block upper triangular order of
+ * strongly connected blocks).  A struct spasm_dm of either library can be released by the other's spasm_dm_free.
  *
  * spasm_solve is deliberately NOT exported: the reference's certificate code calls it from inside its own library
  * (spasm_certificate.c:67,87), and this library is linked first, so exporting it would reroute those calls -- the programs
@@ -59,3 +65,8 @@ struct spasm_csr *spasm_rref(const struct spasm_lu *fact, int *Rqinv) { return s
 struct spasm_csr *spasm_kernel(const struct spasm_lu *fact) { return spasm_hip_kernel(fact); }
 
 struct spasm_csr *spasm_gesv(const struct spasm_lu *fact, const struct spasm_csr *B, bool *ok) { return spasm_hip_gesv(fact, B, ok); }
+
+int spasm_maximum_matching(const struct spasm_csr *A, int *jmatch, int *imatch) { return spasm_hip_maximum_matching(A, jmatch, imatch); }
+int spasm_structural_rank(const struct spasm_csr *A) { return spasm_hip_structural_rank(A); }
+struct spasm_dm *spasm_dulmage_mendelsohn(const struct spasm_csr *A) { return spasm_hip_dulmage_mendelsohn(A); }
+struct spasm_dm *spasm_strongly_connected_components(const struct spasm_csr *A) { return spasm_hip_strongly_connected_components(A); }

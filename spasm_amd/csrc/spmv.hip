@@ -87,6 +87,20 @@ __global__ void xa_fill_kernel(const int64_t *Ap, const int *Aj, const int *Ax, 
 	}
 }
 
+// the fill of a pattern-only image (xa_pattern_image): the row indices alone
+__global__ void xa_fill_pattern_kernel(const int64_t *Ap, const int *Aj, int n, int m, const int64_t *cp, uint32_t *pos, int *ri)
+{
+	const int row = (int) ((blockIdx.x * (int64_t) blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
+	if (row >= n)
+		return;
+	for (int64_t px = Ap[row] + lane; px < Ap[row + 1]; px += 64) {
+		const int j = Aj[px];
+		if (j < 0 || j >= m)
+			continue;
+		ri[cp[j] + atomicAdd(&pos[j], 1u)] = row;
+	}
+}
+
 __global__ void xa_bucket_kernel(const int64_t *cp, int m, int *short_cols, int *long_cols, int *nlist)
 {
 	const int j = blockIdx.x * blockDim.x + threadIdx.x;
@@ -260,6 +274,25 @@ XaPlan *xa_plan_create(const struct spasm_csr *A, const char *who)
 	P->upload_ms = e01;
 	P->build_ms = e12;
 	return P;
+}
+
+// the pattern of A column by column, for the matching (matching.hip): the same count and scan as the plan, a fill without values
+bool xa_pattern_image(const int64_t *d_Ap, const int *d_Aj, int n, int m, int64_t *d_cp, int *d_ri, uint32_t *d_work, int *d_bad,
+                      hipStream_t stream)
+{
+	HIP_CHECK(hipMemsetAsync(d_work, 0, (size_t) std::max(m, 1) * 4 * 2, stream));
+	HIP_CHECK(hipMemsetAsync(d_bad, 0, 4, stream));
+	const unsigned row_blocks = (unsigned) (((int64_t) n * 64 + 255) / 256);
+	if (n > 0 && m > 0)
+		hipLaunchKernelGGL(xa_count_kernel, dim3(row_blocks), dim3(256), 0, stream, d_Ap, d_Aj, n, m, d_work, d_bad);
+	hipLaunchKernelGGL(xa_scan_kernel, dim3(1), dim3(1024), 0, stream, d_work, m, d_cp);
+	if (n > 0 && m > 0)
+		hipLaunchKernelGGL(xa_fill_pattern_kernel, dim3(row_blocks), dim3(256), 0, stream, d_Ap, d_Aj, n, m, d_cp, d_work + std::max(m, 1),
+		                   d_ri);
+	HIP_CHECK(hipGetLastError());
+	int bad = 0;
+	d2h(&bad, d_bad, sizeof(bad), stream);
+	return bad == 0;
 }
 
 void xa_plan_destroy(XaPlan *P)

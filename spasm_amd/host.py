@@ -540,3 +540,114 @@ def factorization_verify(A, F, seeds=(42, 1337, 21011984)):
         L.spasm_hip_csr_free(up)
     res = [bool(v) for v in ok[:len(s)]]
     return res[0] if one else res
+
+
+# ---- maximum matching, Dulmage-Mendelsohn, strongly connected components (spasm_matching.c, spasm_dm.c, spasm_scc.c;
+# spasm_amd/csrc/matching.hip, host_dm.cpp) ----
+
+def _check_pattern(A, what):
+    """the checks the C side would die on, as a ValueError first"""
+    if not isinstance(A, Csr):
+        raise ValueError("spasm_amd.%s: A must be a spasm_amd.Csr" % what)
+    if A.n < 0 or A.m < 0:
+        raise ValueError("spasm_amd.%s: A is %d x %d" % (what, A.n, A.m))
+    if A.p[0] != 0 or np.any(np.diff(A.p) < 0) or len(A.j) < A.nnz:
+        raise ValueError("spasm_amd.%s: the row pointers of A are malformed" % what)
+    j = A.j[:A.nnz]
+    if j.size and (j.min() < 0 or j.max() >= A.m):
+        raise ValueError("spasm_amd.%s: a column index of A lies outside [0, %d)" % (what, A.m))
+
+
+class DM:
+    """struct spasm_dm (spasm.h:74-82) as numpy arrays: row / column permutations p and q, fine block boundaries r and c (nb + 1
+    each), coarse boundaries rr and cc (5 each)."""
+
+    def __init__(self, p, q, r, c, nb, rr, cc):
+        self.p, self.q = (np.ascontiguousarray(v, np.int32) for v in (p, q))
+        self.r, self.c = (np.ascontiguousarray(v, np.int32) for v in (r, c))
+        self.nb = int(nb)
+        self.rr, self.cc = (np.ascontiguousarray(v, np.int32) for v in (rr, cc))
+
+    @staticmethod
+    def _of(ptr, n, m, L):
+        s = ptr.contents
+        nb = int(s.nb)
+        arr = lambda a, k: np.ctypeslib.as_array(a, shape=(k,)).copy() if k else np.zeros(0, np.int32)     # noqa: E731
+        out = DM(arr(s.p, n), arr(s.q, m), arr(s.r, nb + 1), arr(s.c, nb + 1), nb, list(s.rr), list(s.cc))
+        L.spasm_hip_dm_free(ptr)
+        return out
+
+    def blocks(self):
+        """the fine blocks: a list of (rows, columns) of A, in the order of r and c"""
+        return [(self.p[self.r[k]:self.r[k + 1]], self.q[self.c[k]:self.c[k + 1]]) for k in range(self.nb)]
+
+
+def maximum_matching(A):
+    """spasm_maximum_matching (spasm_matching.c:103) on the GPU: (jmatch, imatch, size); jmatch[i] is the column matched to row i,
+    imatch[j] the row matched to column j, -1 when unmatched.  Any maximum matching (not necessarily the reference's)."""
+    _check_pattern(A, "maximum_matching")
+    require_gpu("maximum_matching")
+    jmatch = np.zeros(max(A.n, 1), np.int32)
+    imatch = np.zeros(max(A.m, 1), np.int32)
+    a = view_csr(A)
+    k = lib().spasm_hip_maximum_matching(C.byref(a), _ip(jmatch), _ip(imatch))
+    return jmatch[:A.n], imatch[:A.m], int(k)
+
+
+def structural_rank(A):
+    """the size of a maximum matching of A's pattern (spasm.h:242 declares it; the reference never defines it)"""
+    _check_pattern(A, "structural_rank")
+    require_gpu("structural_rank")
+    a = view_csr(A)
+    return int(lib().spasm_hip_structural_rank(C.byref(a)))
+
+
+def dulmage_mendelsohn(A):
+    """spasm_dulmage_mendelsohn (spasm_dm.c:90) on the GPU: a DM in the reference's layout (q = C0|C1|C2|C3, p = R1|R2|R3|R0;
+    fine blocks H, the strongly connected components of S, V).  When S is empty nb = 2 (the reference: 0)."""
+    _check_pattern(A, "dulmage_mendelsohn")
+    require_gpu("dulmage_mendelsohn")
+    L = lib()
+    a = view_csr(A)
+    return DM._of(L.spasm_hip_dulmage_mendelsohn(C.byref(a)), A.n, A.m, L)
+
+
+def strongly_connected_components(A):
+    """spasm_strongly_connected_components (spasm_scc.c:14) of a square A, on the host: p == q, r == c, A(p, p) block upper
+    triangular with strongly connected blocks"""
+    _check_pattern(A, "strongly_connected_components")
+    if A.n != A.m:
+        raise ValueError("spasm_amd.strongly_connected_components: A is %d x %d, not square" % (A.n, A.m))
+    L = lib()
+    a = view_csr(A)
+    return DM._of(L.spasm_hip_strongly_connected_components(C.byref(a)), A.n, A.n, L)
+
+
+def permute(A, p, qinv, with_values=True):
+    """spasm_permute (spasm_permutation.c:68): row i of the result is row p[i] of A, column j of A is column qinv[j]; p or qinv
+    None: the identity"""
+    _check_pattern(A, "permute")
+    vecs = []
+    for v, k, name in ((p, A.n, "p"), (qinv, A.m, "qinv")):
+        if v is None:
+            vecs.append(None)
+            continue
+        v = np.ascontiguousarray(v, np.int32)
+        if v.shape != (k,) or not np.array_equal(np.sort(v), np.arange(k)):
+            raise ValueError("spasm_amd.permute: %s is not a permutation of 0 .. %d" % (name, k - 1))
+        vecs.append(v if k else np.zeros(1, np.int32))
+    L = lib()
+    a = view_csr(A)
+    out = L.spasm_hip_permute(C.byref(a), *(None if v is None else _ip(v) for v in vecs), 1 if with_values else 0)
+    B = copy_csr(out)
+    L.spasm_hip_csr_free(out)
+    return B
+
+
+def dm_stats():
+    """spasm_hip_dm_stats: the last matching / decomposition call, stage by stage (ms) and its counts"""
+    out = (C.c_double * 13)()
+    lib().spasm_hip_dm_stats(out, 13)
+    keys = ("upload_ms", "greedy_ms", "phases_ms", "reach_ms", "coarse_ms", "scc_ms", "total_ms", "greedy_size", "phases",
+            "levels", "small_levels", "size", "nb")
+    return {k: out[t] for t, k in enumerate(keys)}

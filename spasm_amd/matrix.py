@@ -100,6 +100,12 @@ class CSchurStats(C.Structure):    # spasm_hip_schur_stats
                 ("bytes_sparse_build", C.c_int64), ("bytes_sparse_apply", C.c_int64), ("bytes_sparse_gather", C.c_int64)]
 
 
+class CDm(C.Structure):
+    """struct spasm_dm (spasm.h:74-82)"""
+    _fields_ = [("p", C.POINTER(C.c_int)), ("q", C.POINTER(C.c_int)), ("r", C.POINTER(C.c_int)), ("c", C.POINTER(C.c_int)),
+                ("nb", C.c_int), ("rr", C.c_int * 5), ("cc", C.c_int * 5)]
+
+
 def field_of(prime):
     F = CField()
     F.p = prime
