@@ -889,6 +889,138 @@ template <bool PACKED, bool PLAIN> __global__ __launch_bounds__(512) void bs_app
 //   * the rows of R of the next tile group are in flight while the current one is multiplied;
 //   * the entries are counted while the last batch is applied (no separate pass over the row), the output loop works on
 //     32-bit offsets from a uniform base.
+// One segment of a row of S (words w0 .. w0 + nwords of the packed row) into the LDS buffer xw: the non-pivotal entries of
+// the input row [lo, hi) are added in, the pivotal ones queued in plist and applied.  Returns the entries of the segment,
+// or -1 when the last batch had no pivotal entry (the segment was not swept: the caller counts if it needs them).
+// DEEP: two units of loads in flight while one is multiplied instead of one (for a caller whose occupancy the LDS limits,
+// not the registers).
+template <bool DEEP>
+__device__ __forceinline__ int s16_reduce_segment(const ApplyArgs &d, const MontDev &F, const SgnDev &G, int64_t lo, int64_t hi, int w0, int nwords,
+                                                  uint2 *plist, uint32_t *xw, int lane, bool first_seg, unsigned long long &st_piv)
+{
+	short *xe = reinterpret_cast<short *>(xw);
+	const uint32_t *R = static_cast<const uint32_t *>(d.R);
+	const uint32_t ldw256 = (uint32_t) (d.ldR / 2 / 256);          // row stride of R in units of 256 words (rows are padded to 512 columns):
+	                                                               // the offset of a row in these units fits 32 bits for any R below 4 TB
+	for (int t = lane; t < nwords; t += 64)
+		xw[t] = 0;
+	int npl = 0;                         // entries waiting in plist (wave-uniform)
+	int count = -1;                      // entries of the finished segment, once known
+	for (int64_t base = lo;; base += 64) {
+		bool piv = false;
+		uint32_t cid = 0;
+		int bal = 0;
+		if (base + lane < hi) {
+			cid = (uint32_t) d.col[d.a.Aj[base + lane]];
+			bal = sgn_from_residue(reduce_sum(from_balanced(d.a.Ax[base + lane], F), F), G);
+			if (cid >= (uint32_t) d.r) {
+				const uint32_t t = cid - (uint32_t) d.r - 2u * (uint32_t) w0;          // (unsigned: columns before the segment wrap around)
+				if (t < 2u * (uint32_t) nwords)
+					xe[t] = (short) sgn_canonical((int) xe[t] + bal, G);
+			} else {
+				piv = bal != 0;
+			}
+		}
+		const uint64_t mk = __ballot(piv);
+		if (piv)
+			plist[npl + __popcll(mk & ((1ull << lane) - 1ull))] = uint2{cid * ldw256, (uint32_t) (-bal)};          // (where the row of R starts, in units of 256 words)
+		npl += __popcll(mk);
+		st_piv += first_seg ? (unsigned long long) __popcll(mk) : 0ull;
+		const bool last = base + 64 >= hi;
+		if (npl > 0 && (last || npl + 64 > AP_LIST)) {
+			// apply the queued pivotal entries: x[tile group] += sum_e (-a_e) R[e][tile group], four rows of R at a
+			// time.  A unit = (tile group, four entries of the list); the loads of unit u + 1 are issued before unit
+			// u is multiplied.
+			const int ne = (npl + 3) >> 2;
+			const int nunits = (nwords / (64 * AP_TU)) * ne;
+			int cnt = 0;
+			int alo[AP_TU], ahi[AP_TU];
+			uint32_t wa[4][AP_TU], wb[4][AP_TU], wc[4][AP_TU];
+			int ca[4], cb[4], cc[4];
+			int pf_t0 = 0, pf_e = 0;                 // unit the next issue() will load
+			// (no branch in here: the wait counts of the multiplications are static, and a path that skips an issue
+			//  would force them all to the count of that path.  Past the last unit the last tile group is read again.)
+			const int t0_last = nwords - 64 * AP_TU;
+			const int64_t row_mask = (d.dbg & 8) ? 0 : -1;
+			auto issue = [&](uint32_t (&w)[4][AP_TU], int (&cf)[4]) {
+				const int t0c = (pf_t0 < t0_last) ? pf_t0 : t0_last;
+#pragma unroll
+				for (int q = 0; q < 4; q++) {
+					const int idx = (pf_e + q < npl) ? pf_e + q : npl - 1;
+					const uint2 pe = plist[idx];
+					cf[q] = (pf_e + q < npl) ? (int) pe.y : 0;          // (coefficient 0: no effect)
+					const uint32_t *rq = R + ((((uint64_t) pe.x) << 8) & (uint64_t) row_mask) + w0 + t0c + lane;
+#pragma unroll
+					for (int u = 0; u < AP_TU; u++)
+						w[q][u] = rq[u * 64];          // (rows are padded to whole tile groups)
+				}
+				pf_e += 4;
+				const bool wrap = pf_e >= npl;
+				pf_e = wrap ? 0 : pf_e;
+				pf_t0 += wrap ? 64 * AP_TU : 0;
+			};
+			int t0 = 0, e = 0;                       // unit being multiplied
+			auto multiply = [&](const uint32_t (&w)[4][AP_TU], const int (&cf)[4]) {
+				if (e == 0) {
+#pragma unroll
+					for (int u = 0; u < AP_TU; u++)
+						sgn_unpack(xw[t0 + u * 64 + lane], alo[u], ahi[u]);
+				} else {                 // four terms were added already
+#pragma unroll
+					for (int u = 0; u < AP_TU; u++) {
+						alo[u] = sgn_reduce(alo[u], G);
+						ahi[u] = sgn_reduce(ahi[u], G);
+					}
+				}
+#pragma unroll
+				for (int q = 0; q < 4; q++)
+#pragma unroll
+					for (int u = 0; u < AP_TU; u++)
+						sgn_mad(w[q][u], cf[q], alo[u], ahi[u]);
+				e += 4;
+				if (e >= npl) {
+#pragma unroll
+					for (int u = 0; u < AP_TU; u++) {
+						const int rl = sgn_reduce(alo[u], G), rh = sgn_reduce(ahi[u], G);
+						xw[t0 + u * 64 + lane] = sgn_pack(rl, rh);
+						cnt += __popcll(__ballot(rl != 0)) + __popcll(__ballot(rh != 0));
+					}
+					e = 0;
+					t0 += 64 * AP_TU;
+				}
+			};
+			issue(wa, ca);
+			if constexpr (DEEP) {
+				issue(wb, cb);
+				for (int u = 0; u < nunits; u += 3) {
+					issue(wc, cc);
+					multiply(wa, ca);
+					issue(wa, ca);
+					if (u + 1 < nunits)
+						multiply(wb, cb);
+					issue(wb, cb);
+					if (u + 2 < nunits)
+						multiply(wc, cc);
+				}
+			} else {
+				for (int u = 0; u < nunits; u += 2) {
+					issue(wb, cb);
+					multiply(wa, ca);
+					issue(wa, ca);
+					if (u + 1 < nunits)
+						multiply(wb, cb);
+				}
+			}
+			if (last)
+				count = cnt;
+			npl = 0;
+		}
+		if (last)
+			break;
+	}
+	return count;
+}
+
 __global__ __launch_bounds__(512) void bs_apply_s16_kernel(ApplyArgs d)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -906,9 +1038,6 @@ __global__ __launch_bounds__(512) void bs_apply_s16_kernel(ApplyArgs d)
 	uint2 *plist = reinterpret_cast<uint2 *>(lds_raw + (size_t) wave * d.wave_bytes);
 	uint32_t *xw = reinterpret_cast<uint32_t *>(plist + AP_LIST);
 	short *xe = reinterpret_cast<short *>(xw);
-	const uint32_t *R = static_cast<const uint32_t *>(d.R);
-	const uint32_t ldw256 = (uint32_t) (d.ldR / 2 / 256);          // row stride of R in units of 256 words (rows are padded to 512 columns):
-	                                                               // the offset of a row in these units fits 32 bits for any R below 4 TB
 	const int2 *q2 = reinterpret_cast<const int2 *>(a.q);          // (the array is padded to whole tile groups)
 	unsigned long long st_input = 0, st_piv = 0;
 	int st_done = 0;
@@ -925,108 +1054,7 @@ __global__ __launch_bounds__(512) void bs_apply_s16_kernel(ApplyArgs d)
 		int total = 0;                       // entries of the segments done so far
 	  for (int seg = 0; seg < nseg; seg++) {
 		const int w0 = seg * d.seg_words, nwords = min(d.seg_words, nwords_row - w0);
-		for (int t = lane; t < nwords; t += 64)
-			xw[t] = 0;
-		int npl = 0;                         // entries waiting in plist (wave-uniform)
-		int count = -1;                      // entries of the finished segment, once known
-		for (int64_t base = lo;; base += 64) {
-			bool piv = false;
-			uint32_t cid = 0;
-			int bal = 0;
-			if (base + lane < hi) {
-				cid = (uint32_t) d.col[a.Aj[base + lane]];
-				bal = sgn_from_residue(reduce_sum(from_balanced(a.Ax[base + lane], F), F), G);
-				if (cid >= (uint32_t) d.r) {
-					const uint32_t t = cid - (uint32_t) d.r - 2u * (uint32_t) w0;          // (unsigned: columns before the segment wrap around)
-					if (t < 2u * (uint32_t) nwords)
-						xe[t] = (short) sgn_canonical((int) xe[t] + bal, G);
-				} else {
-					piv = bal != 0;
-				}
-			}
-			const uint64_t mk = __ballot(piv);
-			if (piv)
-				plist[npl + __popcll(mk & ((1ull << lane) - 1ull))] = uint2{cid * ldw256, (uint32_t) (-bal)};          // (where the row of R starts, in units of 256 words)
-			npl += __popcll(mk);
-			st_piv += (seg == 0) ? (unsigned long long) __popcll(mk) : 0ull;
-			const bool last = base + 64 >= hi;
-			if (npl > 0 && (last || npl + 64 > AP_LIST)) {
-				// apply the queued pivotal entries: x[tile group] += sum_e (-a_e) R[e][tile group], four rows of R at a
-				// time.  A unit = (tile group, four entries of the list); the loads of unit u + 1 are issued before unit
-				// u is multiplied.
-				const int ne = (npl + 3) >> 2;
-				const int nunits = (nwords / (64 * AP_TU)) * ne;
-				int cnt = 0;
-				int alo[AP_TU], ahi[AP_TU];
-				uint32_t wa[4][AP_TU], wb[4][AP_TU];
-				int ca[4], cb[4];
-				int pf_t0 = 0, pf_e = 0;                 // unit the next issue() will load
-				// (no branch in here: the wait counts of the multiplications are static, and a path that skips an issue
-				//  would force them all to the count of that path.  Past the last unit the last tile group is read again.)
-				const int t0_last = nwords - 64 * AP_TU;
-				const int64_t row_mask = (d.dbg & 8) ? 0 : -1;
-				auto issue = [&](uint32_t (&w)[4][AP_TU], int (&cf)[4]) {
-					const int t0c = (pf_t0 < t0_last) ? pf_t0 : t0_last;
-#pragma unroll
-					for (int q = 0; q < 4; q++) {
-						const int idx = (pf_e + q < npl) ? pf_e + q : npl - 1;
-						const uint2 pe = plist[idx];
-						cf[q] = (pf_e + q < npl) ? (int) pe.y : 0;          // (coefficient 0: no effect)
-						const uint32_t *rq = R + ((((uint64_t) pe.x) << 8) & (uint64_t) row_mask) + w0 + t0c + lane;
-#pragma unroll
-						for (int u = 0; u < AP_TU; u++)
-							w[q][u] = rq[u * 64];          // (rows are padded to whole tile groups)
-					}
-					pf_e += 4;
-					const bool wrap = pf_e >= npl;
-					pf_e = wrap ? 0 : pf_e;
-					pf_t0 += wrap ? 64 * AP_TU : 0;
-				};
-				int t0 = 0, e = 0;                       // unit being multiplied
-				auto multiply = [&](const uint32_t (&w)[4][AP_TU], const int (&cf)[4]) {
-					if (e == 0) {
-#pragma unroll
-						for (int u = 0; u < AP_TU; u++)
-							sgn_unpack(xw[t0 + u * 64 + lane], alo[u], ahi[u]);
-					} else {                 // four terms were added already
-#pragma unroll
-						for (int u = 0; u < AP_TU; u++) {
-							alo[u] = sgn_reduce(alo[u], G);
-							ahi[u] = sgn_reduce(ahi[u], G);
-						}
-					}
-#pragma unroll
-					for (int q = 0; q < 4; q++)
-#pragma unroll
-						for (int u = 0; u < AP_TU; u++)
-							sgn_mad(w[q][u], cf[q], alo[u], ahi[u]);
-					e += 4;
-					if (e >= npl) {
-#pragma unroll
-						for (int u = 0; u < AP_TU; u++) {
-							const int rl = sgn_reduce(alo[u], G), rh = sgn_reduce(ahi[u], G);
-							xw[t0 + u * 64 + lane] = sgn_pack(rl, rh);
-							cnt += __popcll(__ballot(rl != 0)) + __popcll(__ballot(rh != 0));
-						}
-						e = 0;
-						t0 += 64 * AP_TU;
-					}
-				};
-				issue(wa, ca);
-				for (int u = 0; u < nunits; u += 2) {
-					issue(wb, cb);
-					multiply(wa, ca);
-					issue(wa, ca);
-					if (u + 1 < nunits)
-						multiply(wb, cb);
-				}
-				if (last)
-					count = cnt;
-				npl = 0;
-			}
-			if (last)
-				break;
-		}
+		int count = s16_reduce_segment<false>(d, F, G, lo, hi, w0, nwords, plist, xw, lane, seg == 0, st_piv);
 
 		// ---- output ----
 		if (d.dense_out != nullptr) {
@@ -1127,6 +1155,218 @@ __global__ __launch_bounds__(512) void bs_apply_s16_kernel(ApplyArgs d)
 	  }          // segments
 	}
 	if (lane == 0) {
+		atomicAdd(&a.ctr64[C64_INPUT], st_input);
+		atomicAdd(&a.ctr64[C64_ELIM], st_piv);
+		atomicAdd(&a.ctr[a.done_ctr], st_done);
+	}
+}
+
+// ---- CSR output straight from the apply (signed 16-bit entries, rows of one segment) ---------------------------------------
+// bs_apply_s16_csr_kernel writes every row of S at its final place in Sj / Sx, without the staging pass below.  Each wave owns
+// TWO row buffers.  A finished row publishes its length (look-back status word, as the `direct` output above) and stays in its
+// buffer while the wave computes the next row; at every row boundary the wave takes ONE look, without waiting, whether the
+// offset of its older pending row is known (every row before it has published its length), and once it is, writes that row
+// from LDS.  A wave waits only when both buffers hold rows whose offsets are unknown, and at the end of the batch.  (The
+// `direct` output made every row wait for its slowest running predecessor with its LDS held: a third of its time on mk13.b5.)
+constexpr int CSR_SCRATCH_BYTES = 512 * 4;          // per wave: the list of pivotal entries while a row is computed, the
+                                                    // compaction area of the output (512 ints) while a row is written
+static_assert(CSR_SCRATCH_BYTES >= AP_LIST * (int) sizeof(uint2), "the list shares the compaction area");
+
+// One look back from row k (its length published): the status words of row k and the 63 rows before it, then further back
+// while no end is found.  true: end = offset past row k.  false: a row in between has not published its length yet -- only
+// without `wait`; with it the look is repeated (after 2^24 polls `lost` is set and true returned).  A look that succeeds also
+// publishes the ends of the rows of its first window that had only their lengths, so that the next look stops close by.
+__device__ __forceinline__ bool lookback_probe(const ApplyArgs &d, int k, int lane, bool wait, unsigned long long &end, bool &lost)
+{
+	unsigned long long total = 0, near = 0;          // near: length of this lane's row in the first window (rows before its nearest end)
+	int near_end = -1;                               // position of that end in the first window (-1: window not complete yet)
+	long long polls = 0;
+	for (int j = k; j >= 0;) {
+		const int idx = j - lane;
+		const unsigned long long val = (idx >= 0) ? __hip_atomic_load(&d.status[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : LB_FLAG_END;
+		const uint64_t m_end = __ballot((val >> 62) == 2);
+		const int first_end = m_end ? __builtin_ctzll(m_end) : 64;
+		const bool counts = lane <= first_end;
+		if (__ballot(counts && (val >> 62) == 0) != 0) {          // a row in between has not published its length yet
+			if (!wait)
+				return false;
+			if (++polls > (1ll << 24)) {
+				lost = true;
+				break;
+			}
+			__builtin_amdgcn_s_sleep(2);
+			continue;
+		}
+		unsigned long long v = counts ? (val & LB_VALUE) : 0ull;
+		if (near_end < 0) {
+			near_end = first_end;
+			near = (lane < first_end) ? v : 0ull;
+		}
+		for (int sft = 32; sft >= 1; sft >>= 1) {
+			const uint32_t lo32 = (uint32_t) __shfl_xor((int) (uint32_t) v, sft);
+			const uint32_t hi32 = (uint32_t) __shfl_xor((int) (uint32_t) (v >> 32), sft);
+			v += ((unsigned long long) hi32 << 32) | lo32;
+		}
+		total += v;
+		if (first_end < 64)
+			break;
+		j -= 64;
+	}
+	end = total;
+	if (!lost && near_end > 0) {
+		// the end of row k - lane is `total` less the lengths of the rows after it (the lanes before this one)
+		unsigned long long incl = near;
+		for (int sft = 1; sft < 64; sft <<= 1) {
+			const uint32_t lo32 = (uint32_t) __shfl_up((int) (uint32_t) incl, sft);
+			const uint32_t hi32 = (uint32_t) __shfl_up((int) (uint32_t) (incl >> 32), sft);
+			if (lane >= sft)
+				incl += ((unsigned long long) hi32 << 32) | lo32;
+		}
+		if (lane < near_end)
+			__hip_atomic_store(&d.status[k - lane], LB_FLAG_END | ((total - (incl - near)) & LB_VALUE), __ATOMIC_RELAXED,
+			                   __HIP_MEMORY_SCOPE_AGENT);
+	}
+	return true;
+}
+
+// Rows are handed out by next_ticket(); every workgroup of the grid must be resident (the launcher sees to it).  LDS per wave:
+// CSR_SCRATCH_BYTES, then the two row buffers of Smpad / 2 words.
+__global__ __launch_bounds__(512) void bs_apply_s16_csr_kernel(ApplyArgs d)
+{
+	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+	const SchurArgs &a = d.a;
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const MontDev F = a.F;
+	const SgnDev G = d.G;
+	const int nwords = d.Smpad / 2;                      // the whole row: one segment (a multiple of 64 * AP_TU)
+	unsigned char *area = lds_raw + (size_t) wave * d.wave_bytes;
+	uint2 *plist = reinterpret_cast<uint2 *>(area);
+	int *cbuf = reinterpret_cast<int *>(area);           // (the list is not in use while a row is written)
+	uint32_t *x0 = reinterpret_cast<uint32_t *>(area + CSR_SCRATCH_BYTES), *x1 = x0 + nwords;
+	const int2 *q2 = reinterpret_cast<const int2 *>(a.q) + lane;          // (the array is padded to whole tile groups)
+	unsigned long long st_input = 0, st_piv = 0;
+	int st_done = 0;
+	bool lost = false;
+	// rows whose offset was not known yet, oldest first (-1: none; wave-uniform): k0 in x0, k1 in x1
+	int k0 = -1, c0 = 0, k1 = -1, c1 = 0;
+
+	// row k0 to Sj / Sx once its offset is known (one look, or looks until it is with `wait`); false: not known yet
+	auto settle = [&](bool wait) -> bool {
+		unsigned long long end = 0;
+		if (!lookback_probe(d, k0, lane, wait, end, lost))
+			return false;
+		const int64_t off = (int64_t) (end - (unsigned long long) c0);
+		const bool fits = !lost && end <= (unsigned long long) d.cap;
+		if (lane == 0) {
+			d.Sp[k0] = off;
+			if (k0 == a.nrows - 1)
+				d.Sp[a.nrows] = (int64_t) end;
+			if (!fits)
+				atomicOr(&a.ctr[CTR_STATUS], 1);
+		}
+		if (fits && c0 > 0) {
+			// as bs_expand_kernel: the entries of four tiles are compacted in LDS and leave in stores of 64 consecutive entries
+			// (columns first, then values through the same area); the columns of the next eight tiles are in flight during the stores
+			int *oj = d.Sj + off, *ox = d.Sx + off;
+			const int last = nwords - 64 * AP_TU;
+			uint32_t wpos = 0;
+			int2 qa[AP_TU], qb[AP_TU], qc[AP_TU];
+			auto issue = [&](int t0, int2 (&qq)[AP_TU]) {
+				const int t = (t0 < last) ? t0 : last;
+#pragma unroll
+				for (int u = 0; u < AP_TU; u++)
+					qq[u] = q2[t + 64 * u];
+			};
+			// lane l of a tile holds columns 2 (t0 + l) and 2 (t0 + l) + 1: entries come out sorted by column
+			auto emit = [&](int t0, const int2 (&qq)[AP_TU]) {
+				int v0[AP_TU], v1[AP_TU];
+				uint32_t dst[AP_TU], gpos = 0;
+#pragma unroll
+				for (int u = 0; u < AP_TU; u++) {
+					sgn_unpack(x0[t0 + 64 * u + lane], v0[u], v1[u]);
+					v0[u] = sgn_canonical(v0[u], G);
+					v1[u] = sgn_canonical(v1[u], G);
+					const uint64_t m0 = __ballot(v0[u] != 0), m1 = __ballot(v1[u] != 0);
+					uint32_t at = gpos;
+					at = __builtin_amdgcn_mbcnt_hi((uint32_t) (m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m0, at));
+					at = __builtin_amdgcn_mbcnt_hi((uint32_t) (m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m1, at));
+					dst[u] = at;
+					if (v0[u] != 0)
+						cbuf[at] = qq[u].x;
+					if (v1[u] != 0)
+						cbuf[at + (v0[u] != 0 ? 1u : 0u)] = qq[u].y;
+					gpos += (uint32_t) (__popcll(m0) + __popcll(m1));
+				}
+				for (uint32_t t = lane; t < gpos; t += 64)
+					oj[wpos + t] = cbuf[t];
+#pragma unroll
+				for (int u = 0; u < AP_TU; u++) {
+					if (v0[u] != 0)
+						cbuf[dst[u]] = v0[u];
+					if (v1[u] != 0)
+						cbuf[dst[u] + (v0[u] != 0 ? 1u : 0u)] = v1[u];
+				}
+				for (uint32_t t = lane; t < gpos; t += 64)
+					ox[wpos + t] = cbuf[t];
+				wpos += gpos;
+			};
+			constexpr int GW = 64 * AP_TU;          // words of a group
+			issue(0, qa);
+			issue(GW, qb);
+			for (int t0 = 0; t0 < nwords; t0 += 3 * GW) {
+				issue(t0 + 2 * GW, qc);
+				emit(t0, qa);
+				issue(t0 + 3 * GW, qa);
+				if (t0 + GW < nwords)
+					emit(t0 + GW, qb);
+				issue(t0 + 4 * GW, qb);
+				if (t0 + 2 * GW < nwords)
+					emit(t0 + 2 * GW, qc);
+			}
+		}
+		st_done += fits ? 1 : 0;
+		k0 = k1;
+		c0 = c1;
+		k1 = -1;
+		uint32_t *const t = x0;
+		x0 = x1;
+		x1 = t;
+		return true;
+	};
+
+	for (;;) {
+		if (k0 >= 0)
+			settle(k1 >= 0);               // one look; with both buffers taken, until the older row is written
+		const int k = next_ticket(d, lane);
+		if (k >= a.nrows)
+			break;
+		uint32_t *xw = (k0 < 0) ? x0 : x1;
+		const int i = a.rows[k];
+		const int64_t lo = a.Ap[i], hi = a.Ap[i + 1];
+		st_input += (unsigned long long) (hi - lo);
+		int count = s16_reduce_segment<true>(d, F, G, lo, hi, 0, nwords, plist, xw, lane, true, st_piv);
+		if (count < 0) {                     // no pivotal entry in the last batch: the row was not swept
+			count = 0;
+			for (int t0 = 0; t0 < nwords; t0 += 64) {
+				const uint32_t w = xw[t0 + lane];
+				count += __popcll(__ballot((w & 0xFFFFu) != 0)) + __popcll(__ballot((w >> 16) != 0));
+			}
+		}
+		if (lane == 0)
+			__hip_atomic_store(&d.status[k], LB_FLAG_LEN | (unsigned long long) count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		if (k0 < 0) {
+			k0 = k;
+			c0 = count;
+		} else {
+			k1 = k;
+			c1 = count;
+		}
+	}
+	while (k0 >= 0)
+		settle(true);
+	if (lane == 0) {
+		if (lost)
+			atomicOr(&a.ctr[CTR_STATUS], 4);
 		atomicAdd(&a.ctr64[C64_INPUT], st_input);
 		atomicAdd(&a.ctr64[C64_ELIM], st_piv);
 		atomicAdd(&a.ctr[a.done_ctr], st_done);
@@ -2015,6 +2255,26 @@ bool backsolve_stages_output(const spasm_hip_dfact *F, int64_t *row_bytes)
 	return B.planned && env_int("SPASM_HIP_BS_STAGED", 1) != 0;
 }
 
+// bytes of LDS a wave of bs_apply_s16_csr_kernel needs: the list / compaction area and two row buffers
+static size_t csr_wave_bytes(int64_t ldR)
+{
+	return (size_t) CSR_SCRATCH_BYTES + 2 * (size_t) ldR * 2;
+}
+
+// The staged output of a batch replaced by bs_apply_s16_csr_kernel (rows of S straight to Sj / Sx)?  Signed 16-bit entries,
+// rows of one segment (<= 24,576 columns), the whole batch in one slice of the staging buffer, two rows per wave within what a
+// workgroup may have.  SPASM_HIP_BS_CSR=0 keeps the staged kernels (A/B runs, tests).
+bool backsolve_output_csr(const spasm_hip_dfact *F, int64_t nrows, int64_t stage_rows)
+{
+	const BsImage &B = F->bs;
+	if (!B.valid || !B.sgn || B.ldR > 24576 || stage_rows < nrows || env_int("SPASM_HIP_BS_CSR", 1) == 0)
+		return false;
+	int dev = 0, per_block = 0;
+	HIP_CHECK(hipGetDevice(&dev));
+	HIP_CHECK(hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+	return csr_wave_bytes(B.ldR) <= (size_t) per_block;
+}
+
 // S rows from R: sparse rows into the pool of `a` (dense_out == nullptr) or dense rows.
 void launch_backsolve_apply(const SchurArgs &a, const spasm_hip_dfact *F, uint32_t *dense_out, int64_t ldS, hipStream_t stream,
                             BsDirectOut *direct)
@@ -2059,6 +2319,43 @@ void launch_backsolve_apply(const SchurArgs &a, const spasm_hip_dfact *F, uint32
 			hipLaunchKernelGGL((bs_apply_wide_kernel<false, true>), grid, dim3(64 * AW_NW), 0, stream, d);
 		else
 			hipLaunchKernelGGL((bs_apply_wide_kernel<false, false>), grid, dim3(64 * AW_NW), 0, stream, d);
+		HIP_CHECK(hipGetLastError());
+		return;
+	}
+	if (direct != nullptr && direct->csr && dense_out == nullptr) {
+		// rows of S from their LDS buffers straight to Sj / Sx.  Workgroup shape: the one that puts the most waves on a CU
+		// (160 KB of LDS), the larger workgroup on a tie
+		const size_t per_wave = csr_wave_bytes(B.ldR);
+		int per_block = 0;
+		HIP_CHECK(hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+		int waves = 1, best = 0;
+		for (int w = 1; w <= 8 && (size_t) w * per_wave <= (size_t) per_block; w++) {
+			const int fit = (int) ((size_t) (160 * 1024) / ((size_t) w * per_wave)) * w;
+			if (fit >= best) {
+				best = fit;
+				waves = w;
+			}
+		}
+		d.waves = waves;
+		d.wave_bytes = per_wave;
+		d.seg_words = d.Smpad / 2;
+		const size_t lds = per_wave * (size_t) waves;
+		static size_t configured = 0;
+		if (lds > configured) {
+			HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&bs_apply_s16_csr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+			configured = lds;
+		}
+		// a row's offset waits for the lengths of rows that other workgroups hold: every workgroup of the grid resident
+		int per_cu = 0;
+		HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bs_apply_s16_csr_kernel, 64 * waves, lds));
+		per_cu = std::min(per_cu, (int) ((size_t) (160 * 1024) / lds));
+		if (per_cu < 1)
+			die("launch_backsolve_apply: %zu bytes of LDS per workgroup leave no room for the CSR output", lds);
+		const int blocks = std::max(1, std::min((a.nrows + waves - 1) / waves, prop.multiProcessorCount * per_cu));
+		d.ntickets = std::min(LB_TICKETS, blocks);
+		if (verbose() >= 3)
+			logmsg("[dense image] CSR output: %d workgroups of %d waves, %zu bytes of LDS each, %d per CU\n", blocks, waves, lds, per_cu);
+		hipLaunchKernelGGL(bs_apply_s16_csr_kernel, dim3(blocks), dim3(64 * waves), lds, stream, d);
 		HIP_CHECK(hipGetLastError());
 		return;
 	}

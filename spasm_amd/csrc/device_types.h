@@ -282,6 +282,8 @@ struct BsDirectOut {
 	int64_t *Sp;                  // nrows + 1
 	int *Sj, *Sx;
 	int64_t cap;                  // capacity of Sj / Sx
+	// the rows of S straight from their LDS buffers to Sj / Sx (backsolve.hip: bs_apply_s16_csr_kernel), no staging buffer
+	bool csr = false;
 	// staged output (backsolve.hip): room for stage_rows rows of R's width; nullptr: look-back output
 	uint32_t *stage = nullptr;
 	int64_t stage_rows = 0;

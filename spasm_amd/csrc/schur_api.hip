@@ -40,6 +40,7 @@ void backsolve_plan(const FactPlan &P, spasm_hip_dfact *F, hipStream_t stream);
 void backsolve_free(spasm_hip_dfact *F);
 void backsolve_build(const spasm_hip_dfact *F, hipStream_t stream);
 bool backsolve_stages_output(const spasm_hip_dfact *F, int64_t *row_bytes);
+bool backsolve_output_csr(const spasm_hip_dfact *F, int64_t nrows, int64_t stage_rows);
 void launch_backsolve_apply(const SchurArgs &a, const spasm_hip_dfact *F, uint32_t *dense_out, int64_t ldS, hipStream_t stream,
                             BsDirectOut *direct);
 bool backsolve_wanted(const spasm_hip_dfact *F, bool other_path_forced, int nrows);
@@ -2000,15 +2001,19 @@ int dschur_impl(const spasm_hip_dcsr *A, const int *d_rows, int nrows, const spa
 				if (env_int("SPASM_HIP_STAGE_ROWS", 0) > 0)          // (tests: slices on small inputs)
 					rows_fit = env_int("SPASM_HIP_STAGE_ROWS", 0);
 				out.stage_rows = std::min<int64_t>(nrows, rows_fit);
-				const int64_t need = out.stage_rows * stage_row_bytes;
-				if (W->stage_bytes < need) {
-					if (W->d_stage != nullptr)
-						sh::big_free(W->d_stage);
-					W->d_stage = dalloc<uint32_t>(need / 4);
-					W->stage_bytes = need;
+				if (backsolve_output_csr(F, nrows, out.stage_rows)) {
+					out.csr = true;          // every row of S from the apply kernel straight to its place: no staging buffer
+				} else {
+					const int64_t need = out.stage_rows * stage_row_bytes;
+					if (W->stage_bytes < need) {
+						if (W->d_stage != nullptr)
+							sh::big_free(W->d_stage);
+						W->d_stage = dalloc<uint32_t>(need / 4);
+						W->stage_bytes = need;
+					}
+					out.stage = W->d_stage;
+					out.ev_expand = W->ev[6];
 				}
-				out.stage = W->d_stage;
-				out.ev_expand = W->ev[6];
 			}
 			launch_backsolve_apply(a, F, nullptr, 0, stream, &out);
 			bs_staged_slices = out.staged ? out.slices : 0;
