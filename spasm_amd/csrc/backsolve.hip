@@ -18,7 +18,9 @@
 // rows from the last level to the first, with no communication between workgroups at all.  Inside a
 // workgroup the chain of levels runs in LDS: rows are cut into chunks of <= RING consecutive rows;
 //   phase A: every row of the chunk gathers what it needs from outside the chunk (rows of R that are
-//            final, in HBM) into an LDS ring,
+//            final, in HBM) into an LDS ring; the plan hands those rows over as ready offsets (no multiply per
+//            access), the head of a row -- two offsets, two coefficients -- is read from LDS once, and a row starts
+//            at zero in registers: the few entries of U_n are added to the ring afterwards, by the threads that hold them,
 //   phase B: level by level, rows pick up their dependencies inside the chunk from the ring -- every WAVE
 //            on its own columns of every row, so that the levels need no barrier,
 //   phase C: the ring is written back to R.
@@ -155,6 +157,37 @@ template <int I, int N, typename Fn> __device__ __forceinline__ void bs_static_f
 	}
 }
 
+// ---- the head of a row: its first two dependencies outside its chunk --------------------------------
+// Rows are OFFSETS (row * ldw / 256, see backsolve_kernel), BS_NONE = no such dependency (its coefficient is 0).
+//   p < 2^16 (PLAIN): {offset 0, offset 1, coefficient 0 | coefficient 1 << 16, -}: both coefficients fit 16 bits (the signed
+//                     kernels' v_mad_i32_i16 takes either half of a register as it is), so ONE register per row in flight
+//                     carries them from the read of the head (before the loads are issued) to the arithmetic (after they landed);
+//   otherwise:        {offset 0, coefficient 0, offset 1, coefficient 1}, coefficients in Montgomery form.
+// A dependency is present iff its coefficient is not 0 (entries of U are not).
+template <bool PLAIN> __host__ __device__ __forceinline__ uint4 bs_head(uint32_t off0, uint32_t c0, uint32_t off1, uint32_t c1)
+{
+	if constexpr (PLAIN)
+		return uint4{off0, off1, (c0 & 0xFFFFu) | (c1 << 16), 0u};
+	else
+		return uint4{off0, c0, off1, c1};
+}
+
+// lo (hi) = low (high) half of w * the low (HI = 0) or high (HI = 1) half of c2, added to lo (hi) unless FIRST
+template <int HI, bool FIRST> __device__ __forceinline__ void sgn_mad_half(uint32_t w, uint32_t c2, int &lo, int &hi)
+{
+	if constexpr (FIRST) {
+		static_assert(HI == 0, "the first term takes the low coefficient");
+		asm("v_mad_i32_i16 %0, %1, %2, 0" : "=v"(lo) : "v"(w), "v"(c2));
+		asm("v_mad_i32_i16 %0, %1, %2, 0 op_sel:[1,0,0,0]" : "=v"(hi) : "v"(w), "v"(c2));
+	} else if constexpr (HI == 0) {
+		asm("v_mad_i32_i16 %0, %1, %2, %0" : "+v"(lo) : "v"(w), "v"(c2));
+		asm("v_mad_i32_i16 %0, %1, %2, %0 op_sel:[1,0,0,0]" : "+v"(hi) : "v"(w), "v"(c2));
+	} else {
+		asm("v_mad_i32_i16 %0, %1, %2, %0 op_sel:[0,1,0,0]" : "+v"(lo) : "v"(w), "v"(c2));
+		asm("v_mad_i32_i16 %0, %1, %2, %0 op_sel:[1,1,0,0]" : "+v"(hi) : "v"(w), "v"(c2));
+	}
+}
+
 // LPR lanes (words) per row of a slab: a row of a slab is LPR * 4 bytes (128 B with LPR = 32: whole cache lines, half
 // as many requests as 64-byte segments -- the kernel is bound by the rate of such requests).
 // NW waves per workgroup; a wave instruction covers 64 / LPR rows.
@@ -216,10 +249,14 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 	const int64_t ldw = b.ldR / Word<PACKED>::CPL;       // row stride of R in words
 	uint32_t *Rs = static_cast<uint32_t *>(b.R) + (int64_t) blockIdx.x * LPR + wl;
 	// a row of R starts at row * ldw words; ldw is a multiple of 256 (rows are padded to 512 columns), and row * (ldw / 256)
-	// fits 32 bits for any R below 4 TB: one 32-bit multiply and a shift instead of a 64-bit multiply per load
+	// fits 32 bits for any R below 4 TB.  The plan hands every dependency over as that product (its OFFSET, in units of 256
+	// words): an address is a shift and an add.  The chunk's own rows are the offset of its first row (one scalar multiply
+	// per chunk) plus the lane's own (one multiply per kernel) plus a uniform step per iteration
 	const uint32_t ldw256 = (uint32_t) (ldw >> 8);
-	auto row_at = [&](uint32_t row) -> uint32_t * { return Rs + ((uint64_t) (row * ldw256) << 8); };
+	auto at_off = [&](uint32_t off) -> uint32_t * { return Rs + ((uint64_t) off << 8); };
 	const int slot0 = wave * Geo::RS + rs;          // this lane's row slot within an iteration
+	const uint32_t slot0_off = (uint32_t) slot0 * ldw256;
+	const uint32_t iter_off = (uint32_t) Geo::ROWS_PER_ITER * ldw256;          // (uniform)
 	// lanes that hold a word of a row in phases A and C: all of them when LPR divides 64; and the word must exist (the last
 	// slab of a row may reach beyond the padded row when LPR does not divide its length)
 	const bool lane_ok = lane < Geo::LANES_USED && (int64_t) blockIdx.x * LPR + wl < ldw;
@@ -230,18 +267,7 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 	RegFile<uint2, Geo::N_NEAR> m_near;
 	RegFile<uint4, Geo::N_ROW> m_fh;
 	RegFile<uint4, Geo::N_PTAB> m_ptab;
-	// the first THREADS non-pivotal entries of the next chunk (mk13.b5: 61 per chunk), one per thread; the rest -- if any --
-	// is read when the chunk starts
-	uint2 m_np = uint2{0u, 0u};
-	int m_np_row = 0;
 	auto load_meta = [&](const BsChunk &c) {
-		{
-			const int cnt = c.npn & 0x7FFFFFFF;
-			const uint2 v = b.np[(tid < cnt) ? c.np0 + tid : 0];
-			const int vr = b.np_row[(tid < cnt) ? c.np0 + tid : 0];
-			m_np = v;
-			m_np_row = vr;
-		}
 		bs_static_for<0, Geo::N_NEAR>([&](auto qq) {
 			constexpr int q = decltype(qq)::value;
 			const int t = tid + q * Geo::THREADS;
@@ -255,7 +281,7 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 			constexpr int q = decltype(qq)::value;
 			const int t = tid + q * Geo::THREADS;
 			const uint4 v = b.far_head[(t < c.hi - c.lo) ? c.lo + t : 0];
-			m_fh.template at<q>() = (t < c.hi - c.lo) ? v : uint4{BS_NONE, 0u, BS_NONE, 0u};
+			m_fh.template at<q>() = (t < c.hi - c.lo) ? v : bs_head<PLAIN>(BS_NONE, 0u, BS_NONE, 0u);
 		});
 		bs_static_for<0, Geo::N_PTAB>([&](auto qq) {
 			constexpr int q = decltype(qq)::value;
@@ -313,8 +339,6 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 		load_meta(ch_next);
 		store_meta();
 	}
-	uint2 c_np = m_np;            // (chunk 0's own first entries)
-	int c_np_row = m_np_row;
 	if (b.nchunks > 1)
 		fetch_chunk(1);
 	__syncthreads();
@@ -335,9 +359,14 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 	for (int k = 0; k < b.nchunks; k++) {
 		const BsChunk ch = ch_next;
 		const int nrows = ch.hi - ch.lo;
-		if (k > 0) {
-			c_np = m_np;
-			c_np_row = m_np_row;
+		// the first THREADS non-pivotal entries of the chunk (mk13.b5: 61 per chunk), one per thread: asked for now, added to the
+		// rows after phase A; the rest -- if any -- is read then
+		uint2 c_np = uint2{0u, 0u};
+		int c_np_row = 0;
+		if (b.sparse_init) {
+			const int cnt = ch.npn & 0x7FFFFFFF;
+			c_np = b.np[(tid < cnt) ? ch.np0 + tid : 0];
+			c_np_row = b.np_row[(tid < cnt) ? ch.np0 + tid : 0];
 		}
 		if (k + 1 < b.nchunks) {
 			ch_next = fetched_chunk();
@@ -347,17 +376,118 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 			fetch_chunk(k + 2);
 		tick(0);          // descriptor + issue of the next chunk's metadata
 
+		// ---- phase A: own row + dependencies outside the chunk, up to 3 * UNR loads in flight per lane ----
+		// SPARSE (sparse_init): the rows start at zero IN REGISTERS -- R is not read for them, the ring is neither zeroed nor read --
+		// and the few entries of U_n are added to the ring afterwards.  Otherwise a row starts as what bs_init_kernel put into R.
+		const uint32_t lo_off = (uint32_t) ch.lo * ldw256;          // (uniform: a scalar multiply)
+		auto phase_a = [&](auto sparse_tag) {
+			constexpr bool SPARSE = decltype(sparse_tag)::value;
+			for (int pass = 0; pass < Geo::ITERS / Geo::UNR; pass++) {
+				if (pass * Geo::UNR * Geo::ROWS_PER_ITER >= nrows)
+					break;
+				// SPARSE: the coefficients of the head are read with its addresses and kept until the loads have landed (the head is read
+				// once).  The pre-filled path has the row's own word in flight as well: no registers for them, it reads them again;
+				// so do 32-bit coefficients in the workgroups of sixteen waves.
+				constexpr bool KEEP = SPARSE && (PLAIN || NW < 16);          // (sixteen waves have 128 registers each)
+				uint32_t acc[SPARSE ? 1 : Geo::UNR], v0[Geo::UNR], v1[Geo::UNR], c0[KEEP ? Geo::UNR : 1], c1[(KEEP && !PLAIN) ? Geo::UNR : 1];
+				// offset of the lane's own row, stepped from iteration to iteration (hidden from the compiler's algebra, which
+				// would turn the sum back into (first row + slot) * stride: a quarter-rate multiply per access)
+				uint32_t own_off = lo_off + (uint32_t) (pass * Geo::UNR) * iter_off + slot0_off;
+				asm volatile("" : "+v"(own_off));
+#pragma unroll
+				for (int u = 0; u < Geo::UNR; u++) {
+					const int s = (pass * Geo::UNR + u) * Geo::ROWS_PER_ITER + slot0;
+					const bool ok = s < nrows && lane_ok;
+					const uint4 h = fh[ok ? s : 0];
+					const uint32_t a0 = h.x, a1 = PLAIN ? h.y : h.z;
+					if constexpr (KEEP) {
+						c0[u] = PLAIN ? h.z : h.y;
+						if constexpr (!PLAIN)
+							c1[u] = h.w;
+					}
+					if constexpr (!SPARSE) {
+						acc[u] = ok ? *at_off(own_off) : 0u;
+						own_off += iter_off;
+					}
+					if constexpr (LPR <= 16 && 64 % LPR == 0) {
+						// no branch around the loads: an absent dependency reads the chunk's own first row -- a valid address -- and
+						// is multiplied by the coefficient 0 of its slot, or skipped, below (64-byte rows: 2.84 -> 2.75 ms on mk13.b5,
+						// 9.2 -> 6.1 ms with 32-bit entries; with 128-byte rows the wasted lines cost more than the branches)
+						v0[u] = *at_off((ok && a0 != BS_NONE) ? a0 : lo_off);
+						v1[u] = *at_off((ok && a1 != BS_NONE) ? a1 : lo_off);
+					} else {
+						v0[u] = (ok && a0 != BS_NONE) ? *at_off(a0) : 0u;
+						v1[u] = (ok && a1 != BS_NONE) ? *at_off(a1) : 0u;
+					}
+				}
+#pragma unroll
+				for (int u = 0; u < Geo::UNR; u++) {
+					const int s = (pass * Geo::UNR + u) * Geo::ROWS_PER_ITER + slot0;          // (< RING: a head that exists, whatever it holds)
+					uint32_t x = SPARSE ? 0u : acc[u];
+					uint32_t k0, k1;          // coefficients: both in k0 when PLAIN
+					if constexpr (KEEP) {
+						k0 = c0[u];
+						k1 = PLAIN ? 0u : c1[u];
+					} else if constexpr (PLAIN) {
+						k0 = fh[s].z;
+						k1 = 0u;
+					} else {
+						const uint4 h = fh[s];
+						k0 = h.y;
+						k1 = h.w;
+					}
+					if constexpr (SGN) {
+						// no flags: an absent dependency has the coefficient 0 (and was loaded as 0, or as a row that exists), and a row
+						// without dependencies comes out of the reduction as it went in (|x| <= p/2: the nearest multiple of p is 0)
+						int lo, hi;
+						if constexpr (SPARSE) {
+							sgn_mad_half<0, true>(v0[u], k0, lo, hi);
+						} else {
+							sgn_unpack(x, lo, hi);
+							sgn_mad_half<0, false>(v0[u], k0, lo, hi);
+						}
+						sgn_mad_half<1, false>(v1[u], k0, lo, hi);
+						x = sgn_pack(sgn_reduce(lo, G), sgn_reduce(hi, G));
+					} else {
+						if constexpr (PLAIN) {
+							k1 = k0 >> 16;
+							k0 &= 0xFFFFu;
+						}
+						if (k0 != 0u)
+							x = w_submul<PACKED, PLAIN>(x, v0[u], k0, F, bm);
+						if (k1 != 0u)
+							x = w_submul<PACKED, PLAIN>(x, v1[u], k1, F, bm);
+					}
+					if (s < nrows && lane_ok)
+						ring[s * RSTR + wl] = x;
+				}
+			}
+		};
+		if (b.sparse_init)
+			phase_a(std::true_type{});
+		else
+			phase_a(std::false_type{});
+		lds_barrier();
+		tick(1);          // phase A
 		if (b.sparse_init) {
-			// the rows start as U_n: few entries, scattered from the list (R itself is never read for them)
-			for (int t = tid; t < nrows * RSTR; t += Geo::THREADS)
-				ring[t] = 0;
-			lds_barrier();
+			// the entries of U_n, from the list, each added to its element of the ring by the thread that holds it (distinct rows and
+			// columns are distinct elements: no two threads meet).  The sum is brought back into the range of an entry.
 			const int np_count = ch.npn & 0x7FFFFFFF;
 			auto put = [&](const uint2 en, int row) {
 				const int cc = (int) en.x - col_lo;
-				if (cc >= 0 && cc < Geo::CW)
-					reinterpret_cast<Elem *>(ring)[(row - ch.lo) * (RSTR * Word<PACKED>::CPL) + cc] =
-						SGN ? (Elem) (uint16_t) (int16_t) sgn_from_residue(en.y, G) : (Elem) (PLAIN ? en.y : montmul(en.y, 1u, F));
+				if (cc >= 0 && cc < Geo::CW) {
+					Elem *at = reinterpret_cast<Elem *>(ring) + (row - ch.lo) * (RSTR * Word<PACKED>::CPL) + cc;
+					if constexpr (SGN) {
+						// |entry| <= p/2 + p/64 + 1, |U_n| <= p/2: one step brings the sum into [-p/2, p/2]
+						*at = (Elem) (uint16_t) (int16_t) sgn_canonical((int) (int16_t) *at + sgn_from_residue(en.y, G), G);
+					} else {
+						const uint32_t v = PLAIN ? en.y : montmul(en.y, 1u, F);
+						uint32_t sum = (uint32_t) *at + v;
+						if (sum < v || sum >= F.p)
+							sum -= F.p;
+						*at = (Elem) sum;
+					}
+				}
 			};
 			if (tid < np_count)
 				put(c_np, c_np_row);
@@ -365,58 +495,7 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 				put(b.np[ch.np0 + e], b.np_row[ch.np0 + e]);
 			lds_barrier();
 		}
-		tick(1);          // start of the rows (zero + scatter of the non-pivotal entries)
-
-		// ---- phase A: own row + dependencies outside the chunk, up to 3 * UNR loads in flight per lane ----
-		for (int pass = 0; pass < Geo::ITERS / Geo::UNR; pass++) {
-			if (pass * Geo::UNR * Geo::ROWS_PER_ITER >= nrows)
-				break;
-			uint32_t acc[Geo::UNR], v0[Geo::UNR], v1[Geo::UNR];
-#pragma unroll
-			for (int u = 0; u < Geo::UNR; u++) {
-				const int s = (pass * Geo::UNR + u) * Geo::ROWS_PER_ITER + slot0;
-				const bool ok = s < nrows && lane_ok;
-				const uint4 h = fh[ok ? s : 0];
-				const int c = ch.lo + (ok ? s : 0);
-				acc[u] = (b.sparse_init || !ok) ? 0u : *row_at((uint32_t) c);
-				if constexpr (LPR <= 16 && 64 % LPR == 0) {
-					// no branch around the loads: an absent dependency reads the chunk's own first row -- a valid address -- and
-					// is multiplied by the coefficient 0 of its slot, or skipped, below (64-byte rows: 2.84 -> 2.75 ms on mk13.b5,
-					// 9.2 -> 6.1 ms with 32-bit entries; with 128-byte rows the wasted lines cost more than the branches)
-					v0[u] = *row_at((ok && h.x != BS_NONE) ? h.x : (uint32_t) ch.lo);
-					v1[u] = *row_at((ok && h.z != BS_NONE) ? h.z : (uint32_t) ch.lo);
-				} else {
-					v0[u] = (ok && h.x != BS_NONE) ? *row_at(h.x) : 0u;
-					v1[u] = (ok && h.z != BS_NONE) ? *row_at(h.z) : 0u;
-				}
-			}
-#pragma unroll
-			for (int u = 0; u < Geo::UNR; u++) {
-				const int s = (pass * Geo::UNR + u) * Geo::ROWS_PER_ITER + slot0;
-				if (s < nrows && lane_ok) {
-					const uint4 h = fh[s];
-					uint32_t x = b.sparse_init ? ring[s * RSTR + wl] : acc[u];
-					if constexpr (SGN) {
-						// (an absent dependency was loaded as 0: its term vanishes whatever the coefficient slot holds)
-						if (h.x != BS_NONE) {
-							int lo, hi;
-							sgn_unpack(x, lo, hi);
-							sgn_mad(v0[u], (int) h.y, lo, hi);
-							sgn_mad(v1[u], (int) h.w, lo, hi);
-							x = sgn_pack(sgn_reduce(lo, G), sgn_reduce(hi, G));
-						}
-					} else {
-						if (h.x != BS_NONE)
-							x = w_submul<PACKED, PLAIN>(x, v0[u], h.y, F, bm);
-						if (h.z != BS_NONE)
-							x = w_submul<PACKED, PLAIN>(x, v1[u], h.w, F, bm);
-					}
-					ring[s * RSTR + wl] = x;
-				}
-			}
-		}
-		lds_barrier();
-		tick(2);          // phase A
+		tick(2);          // non-pivotal entries of U added to the rows
 		if (ch.npn < 0) {          // (bit 31 of the descriptor)
 			// rows with more than two outside dependencies (long rows of U): the rest of their lists
 			for (int s = slot0; s < nrows; s += Geo::ROWS_PER_ITER) {
@@ -432,7 +511,7 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 #pragma unroll
 						for (int t = 0; t < 4; t++) {
 							const uint2 en = (e + t < e1) ? b.far[e + t] : uint2{0u, 0u};
-							sgn_mad((e + t < e1) ? *row_at(en.x) : 0u, (int) en.y, lo, hi);
+							sgn_mad((e + t < e1) ? *at_off(en.x) : 0u, (int) en.y, lo, hi);          // (en.x: the row's offset)
 						}
 						lo = sgn_reduce(lo, G);
 						hi = sgn_reduce(hi, G);
@@ -441,7 +520,7 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 				} else {
 					for (uint64_t e = e0; e < e1; e++) {
 						const uint2 en = b.far[e];
-						x = w_submul<PACKED, PLAIN>(x, *row_at(en.x), en.y, F, bm);
+						x = w_submul<PACKED, PLAIN>(x, *at_off(en.x), en.y, F, bm);
 					}
 				}
 				ring[s * RSTR + wl] = x;
@@ -551,9 +630,13 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 		tick(4);          // phase B
 
 		// ---- phase C: write the chunk back ----
-		for (int s = slot0; s < nrows; s += Geo::ROWS_PER_ITER)
-			if (lane_ok)
-				*row_at((uint32_t) (ch.lo + s)) = ring[s * RSTR + wl];
+		{
+			uint32_t off = lo_off + slot0_off;
+			asm volatile("" : "+v"(off));          // (as in phase A: stepped, not multiplied)
+			for (int s = slot0; s < nrows; s += Geo::ROWS_PER_ITER, off += iter_off)
+				if (lane_ok)
+					*at_off(off) = ring[s * RSTR + wl];
+		}
 		__syncthreads();          // (workgroup-scope release/acquire: later chunks read these rows; LDS metadata is free)
 		tick(5);          // phase C
 		if (k + 1 < b.nchunks)
@@ -1908,7 +1991,12 @@ void backsolve_plan(const FactPlan &P, spasm_hip_dfact *F, hipStream_t stream)
 	std::vector<int> chunk_extra;
 	std::vector<uint4> ptab;
 	std::vector<uint2> near;
-	std::vector<uint4> far_head((size_t) (r > 0 ? r : 1), uint4{BS_NONE, 0u, BS_NONE, 0u});
+	// rows of R go to the kernel as offsets, row * (words of a row / 256): see backsolve_kernel
+	const uint32_t ldw256 = (uint32_t) ((B.ldR / (P.prime < 65536 ? 2 : 1)) >> 8);
+	if ((uint64_t) (r > 0 ? r : 1) * ldw256 >= (uint64_t) BS_NONE)
+		die("backsolve_plan: %d rows of %lld columns: the offset of a row does not fit 32 bits", r, (long long) B.ldR);
+	auto make_head = [&](uint32_t off0, uint32_t c0, uint32_t off1, uint32_t c1) { return B.plain ? bs_head<true>(off0, c0, off1, c1) : bs_head<false>(off0, c0, off1, c1); };
+	std::vector<uint4> far_head((size_t) (r > 0 ? r : 1), make_head(BS_NONE, 0u, BS_NONE, 0u));
 	std::vector<uint64_t> far_rp((size_t) r + 1, 0);
 	std::vector<uint2> far;
 	std::vector<uint64_t> far_cnt((size_t) (r > 0 ? r : 1), 0);
@@ -1966,16 +2054,13 @@ void backsolve_plan(const FactPlan &P, spasm_hip_dfact *F, hipStream_t stream)
 			int last_level = -1, extra = 0, in_level = 0;
 			for (int c = ch.hi - 1; c >= ch.lo; c--) {
 				int nc = 0, nf = 0;
+				uint2 first[2] = {uint2{BS_NONE, 0u}, uint2{BS_NONE, 0u}};
 				for (uint64_t e = dep_rp[c]; e < dep_rp[c + 1]; e++) {
 					if (dep[e].x < (uint32_t) ch.hi) {
 						nc += 1;
 					} else {
-						if (nf == 0) {
-							far_head[c].x = dep[e].x;
-							far_head[c].y = dep[e].y;
-						} else if (nf == 1) {
-							far_head[c].z = dep[e].x;
-							far_head[c].w = dep[e].y;
+						if (nf < 2) {
+							first[nf] = uint2{dep[e].x * ldw256, dep[e].y};
 						} else {
 							far_cnt[c] += 1;
 							extra = 1;
@@ -1983,6 +2068,8 @@ void backsolve_plan(const FactPlan &P, spasm_hip_dfact *F, hipStream_t stream)
 						nf += 1;
 					}
 				}
+				if (nf > 0)
+					far_head[c] = make_head(first[0].x, first[0].y, first[1].x, first[1].y);
 				if (nc == 0)
 					continue;
 				if (level[c] != last_level || in_level % PLAN_PASSROWS == 0) {
@@ -2050,13 +2137,39 @@ void backsolve_plan(const FactPlan &P, spasm_hip_dfact *F, hipStream_t stream)
 			for (uint64_t e = dep_rp[c]; e < dep_rp[c + 1]; e++)
 				if (dep[e].x >= (uint32_t) chunk_hi[c]) {
 					if (nf >= 2)
-						far[w++] = dep[e];
+						far[w++] = uint2{dep[e].x * ldw256, dep[e].y};
 					nf += 1;
 				}
 		}
 	}
 
 	lap("chunks, passes, near and far tables");
+	if (verbose() >= 3) {
+		// how full the passes of phase B are (an empty slot costs a lane what a row does), and why: the widths of the levels
+		int64_t passes = 0, used = 0;
+		for (const BsChunk &ch : chunks)
+			passes += ch.npass;
+		for (const uint4 &en : ptab)
+			used += (en.x >> 16) != 0;
+		logmsg("[factor image/back-substitution plan] shape %d: %zu chunks of <= %d rows, %lld passes of %d slots, %lld of %lld slots occupied (%.1f%%), "
+		       "%d rows in %d levels\n", B.shape, chunks.size(), PLAN_RING, (long long) passes, PLAN_PASSROWS, (long long) used,
+		       (long long) passes * PLAN_PASSROWS, passes > 0 ? 100.0 * (double) used / (double) (passes * PLAN_PASSROWS) : 0.0, r, P.nlevels);
+		int64_t hist_levels[32] = {0}, hist_rows[32] = {0};          // bucket b: widths in (2^(b-1), 2^b]
+		for (int l = 0; l < P.nlevels; l++) {
+			const int w = P.lvl_count[l];
+			if (w <= 0)
+				continue;
+			int bkt = 0;
+			while ((1ll << bkt) < w)
+				bkt += 1;
+			hist_levels[bkt] += 1;
+			hist_rows[bkt] += w;
+		}
+		for (int bkt = 0; bkt < 32; bkt++)
+			if (hist_levels[bkt] > 0)
+				logmsg("[factor image/back-substitution plan]   levels of %lld..%lld rows: %lld levels, %lld rows\n", bkt == 0 ? 1ll : (1ll << (bkt - 1)) + 1,
+				       1ll << bkt, (long long) hist_levels[bkt], (long long) hist_rows[bkt]);
+	}
 	B.nchunks = (int) chunks.size();
 	B.nnear = (int64_t) near.size();
 	B.nfar = (int64_t) far_rp[r];
@@ -2234,7 +2347,7 @@ void backsolve_build(const spasm_hip_dfact *F, hipStream_t stream)
 		unsigned long long h[8];
 		HIP_CHECK(hipMemcpyAsync(h, b.prof, sizeof(h), hipMemcpyDeviceToHost, stream));
 		HIP_CHECK(hipStreamSynchronize(stream));
-		static const char *const stage[7] = {"descriptor + metadata issue", "row start (zero + scatter)", "phase A", "long outside lists", "phase B", "phase C",
+		static const char *const stage[7] = {"descriptor + metadata issue", "phase A", "non-pivotal entries added", "long outside lists", "phase B", "phase C",
 		                                     "metadata into LDS"};
 		unsigned long long tot = 0;
 		for (int q = 0; q < 7; q++)

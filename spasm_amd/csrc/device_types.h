@@ -152,7 +152,7 @@ struct BsImage {
 	uint4 *d_ptab = nullptr;          // 32 entries per pass: (slot | count << 16, dep0 | dep1 << 16, coefficient 0, coefficient 1); a row
 	                                  // with more than two dependencies keeps the first inline, (offset into d_near - near0) in .w, the others there
 	uint2 *d_near = nullptr;          // (slot of the dependency, coefficient)
-	uint4 *d_far_head = nullptr;      // per compact row: its first two dependencies outside the chunk (t0, y0, t1, y1); t = ~0: none
+	uint4 *d_far_head = nullptr;      // per compact row: its first two dependencies outside the chunk, rows as offsets (bs_head in backsolve.hip); ~0: none
 	uint64_t *d_far_rp = nullptr;     // per compact row: the others, [r + 1] offsets into d_far
 	uint2 *d_far = nullptr;
 	uint64_t *d_np_rp = nullptr;      // per compact row: non-pivotal entries (index among the non-pivotal columns, value * 2^32 mod p)
