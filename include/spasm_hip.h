@@ -39,7 +39,9 @@
  *   SPASM_HIP_SPARSE_IMAGE_GB=n   cap of the fragment pool of the sparse image (default: a third of the free HBM, at most half
  *                                 the bytes of the dense form)
  * Every other SPASM_HIP_* name in the sources picks a kernel variant, a debugging aid or a code path kept for A/B runs and
- * tests; they are ignored (with one warning) unless SPASM_HIP_EXPERIMENT=1 is set as well.
+ * tests; they are ignored (with one warning) unless SPASM_HIP_EXPERIMENT=1 is set as well.  Among them:
+ *   SPASM_HIP_SOLVE_BATCH=n       spasm_hip_solver_gesv solves at most n right-hand sides per batch (n rounded down to a multiple of
+ *                                 64, at least 64; default: what half the free HBM holds) -- the tests' way to several batches
  */
 #ifndef SPASM_HIP_H
 #define SPASM_HIP_H
@@ -279,7 +281,9 @@ void spasm_hip_solver_destroy(spasm_hip_solver *S);
 void spasm_hip_solver_levels(const spasm_hip_solver *S, int *out);
 /* the plan and the last solve: [0] seconds of create, device ms of [1] the scatter of B, [2] F, [3] C, [4] B, [5] the emission
  * of X; launches of [6] F, [7] B, [8] everything; [9] algorithmic bytes of the three sweeps; [10] batches, [11] right-hand
- * sides per batch (sized against the free device memory).  Returns how many there are (16, the rest 0). */
+ * sides per batch (sized against the free device memory); of the plan, per batch: launches of [12] F, [13] B that share each
+ * dependency list over a workgroup, launches of [14] F, [15] B that step through several levels (a launch can be both).
+ * Returns how many there are (16). */
 int spasm_hip_solver_stats(const spasm_hip_solver *S, double *out, int count);
 
 /* --- products x.A and rank certificates (replace spasm_spmv.c:9-21, spasm_certificate.c:21-270; spasm_amd/csrc/spmv.hip,

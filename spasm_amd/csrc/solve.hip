@@ -631,6 +631,20 @@ int spasm_hip_solver_stats(const spasm_hip_solver *S, double *out, int count)
 		out[t] = S->last[t];
 	if (count > 0)
 		out[0] = S->plan_seconds;
+	// [12] [13] launches of F and of B that share each list over a workgroup, [14] [15] that step through a run of thin levels
+	// (properties of the plan: there before the first gesv)
+	const SweepPlan *P[2] = {&S->F, &S->B};
+	for (int h = 0; h < 2; h++) {
+		int split = 0, run = 0;
+		for (size_t t = 0; t < P[h]->steps.size(); t++) {
+			split += P[h]->split[t] != 0;
+			run += P[h]->steps[t].y - P[h]->steps[t].x > 1;
+		}
+		if (12 + h < k)
+			out[12 + h] = split;
+		if (14 + h < k)
+			out[14 + h] = run;
+	}
 	return 16;
 }
 
@@ -660,6 +674,9 @@ struct spasm_csr *spasm_hip_solver_gesv(spasm_hip_solver *S, const struct spasm_
 	mem_info(&free_b, &total_b);
 	int64_t kb_max = (int64_t) (free_b / 2) / per_rhs / 64 * 64;
 	kb_max = std::max<int64_t>(64, std::min<int64_t>(kb_max, (int64_t) 65535 * 64));
+	const int batch_env = env_int("SPASM_HIP_SOLVE_BATCH", 0);          // (tests: several batches on small inputs)
+	if (batch_env > 0)
+		kb_max = std::min<int64_t>(kb_max, std::max(64, batch_env / 64 * 64));
 	const int kb_cap = (int) std::min<int64_t>(kb_max, ((int64_t) std::max(k, 1) + 63) / 64 * 64);
 	const int nblk_cap = kb_cap / 64;
 	uint32_t *d_Bd = (uint32_t *) big_alloc((size_t) nblk_cap * 64 * std::max<int64_t>(std::max<int64_t>(m, r), 1) * 4);

@@ -324,11 +324,14 @@ class Solver:
         return _gesv_call(lambda b, ok: lib().spasm_hip_solver_gesv(S, b, ok), B)
 
     def stats(self):
-        """spasm_hip_solver_stats: the plan's seconds and the last gesv's device ms per sweep, launches, bytes, batches."""
+        """spasm_hip_solver_stats: the plan's seconds and the last gesv's device ms per sweep, launches, bytes, batches; of the
+        plan, per batch: the launches of each sweep that split every dependency list over a workgroup, and those that step
+        through a run of levels."""
         out = (C.c_double * 16)()
         lib().spasm_hip_solver_stats(self._S, out, 16)
         keys = ("plan_s", "scatter_ms", "forward_ms", "check_ms", "back_ms", "emit_ms", "forward_launches", "back_launches",
-                "launches", "sweep_bytes", "batches", "rhs_per_batch")
+                "launches", "sweep_bytes", "batches", "rhs_per_batch", "forward_split_launches", "back_split_launches",
+                "forward_run_launches", "back_run_launches")
         return {k: out[t] for t, k in enumerate(keys)}
 
     def close(self):
