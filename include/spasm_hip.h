@@ -42,6 +42,12 @@
  * tests; they are ignored (with one warning) unless SPASM_HIP_EXPERIMENT=1 is set as well.  Among them:
  *   SPASM_HIP_SOLVE_BATCH=n       spasm_hip_solver_gesv solves at most n right-hand sides per batch (n rounded down to a multiple of
  *                                 64, at least 64; default: what half the free HBM holds) -- the tests' way to several batches
+ *   SPASM_HIP_TRANSPOSE_SHORT=n   spasm_hip_dtranspose: a column of at most n entries (1 .. 1024, default 256) is put in order by one
+ *                                 wave (every key ranked against the others in LDS), a longer one by a workgroup (bitmap of its rows)
+ *   SPASM_HIP_TRANSPOSE_CHUNK=n   ... rows per bitmap of that workgroup (rounded up to a multiple of 32; 32 .. 262144, the default):
+ *                                 a matrix with more rows takes its long columns chunk by chunk -- the tests' way to every route
+ *   SPASM_HIP_KERNEL_POOL=n       spasm_hip_kernel_basis: entries of the first pool handed to spasm_hip_dschur (default: the rule of
+ *                                 spasm_hip_schur) -- the tests' way to the retry with a larger pool
  */
 #ifndef SPASM_HIP_H
 #define SPASM_HIP_H
@@ -259,6 +265,26 @@ int spasm_hip_echelonize_counters(long long *out, int count);
 struct spasm_csr *spasm_hip_rref(const struct spasm_lu *fact, int *Rqinv);
 struct spasm_csr *spasm_hip_kernel(const struct spasm_lu *fact);
 
+/* --- kernel bases formed on the device, stable transposition (spasm_amd/csrc/kernel_basis.hip, transpose.hip) ---
+ * the array spasm_hip_kernel returns on the same fact, bit for bit (rows by increasing non-pivotal column j; in a row first
+ * (j, -1), then (pivot column of row i of U, R[i][j]) by increasing i) -- with R, its transpose and K formed on the device: the
+ * rows of U without their pivots go through spasm_hip_dschur against the whole of U (a pool that was too small: again with a
+ * larger one), spasm_hip_dtranspose, one assembly kernel, one download.  Any odd p < 2^32; rank 0 gives -I, full column rank a
+ * matrix of 0 rows.  Dies on a U whose rows do not start with distinct pivots. */
+struct spasm_csr *spasm_hip_kernel_basis(const struct spasm_lu *fact);
+/* the last call: ms of [0] uploads + factor image, [1] the rows of R (spasm_hip_dschur), [2] transposition, [3] assembly of K,
+ * [4] download, [5] the whole call; [6] nnz(K), [7] pool retries, [8] rows of K.  Returns how many there are (9). */
+int spasm_hip_kernel_stats(double *out, int count);
+/* host-pointer twin of spasm_hip_dtranspose (section D): upload, transpose on the device, download; the result is malloc'ed like
+ * spasm_hip_transpose's and equal to it array for array (x absent when keep_values is 0 or A->x is NULL).  Any modulus: the
+ * values are not looked at.  Dies on row pointers that decrease, a column index outside [0, A->m), a repeated (i, j). */
+struct spasm_csr *spasm_hip_transpose_device(const struct spasm_csr *A, int keep_values);
+/* the last transposition (either entry point): ms of [0] upload, [1] count + scan, [2] fill, [3] ordering, [4] download ([0] and
+ * [4] are 0 after spasm_hip_dtranspose); [5] columns put in order by the short route (one wave), [6] by the long route (one
+ * workgroup; empty columns take neither), [7] entries of the longest column, [8] row chunks of the long route (0 when no column
+ * took it).  Returns how many there are (9). */
+int spasm_hip_transpose_stats(double *out, int count);
+
 /* --- solving X.A = B over the factorization (replace spasm_solve.c:13, :52; spasm_amd/csrc/solve.hip) ---
  * fact must come from an echelonization with opts->L = 1: fact->L (rows of A x rank) and fact->p (pivot j of L sits on row
  * p[j]).  Three sweeps on the device, every right-hand side of a call at once: F (z.U = b on the pivot columns), C (is b in the
@@ -468,6 +494,15 @@ int spasm_hip_dschur(const spasm_hip_dcsr *A, const int *d_rows, int nrows, cons
 void spasm_hip_dschur_fetch(const spasm_hip_dwork *W, i64 *d_Sp, int *d_Sj, spasm_ZZp *d_Sx, void *stream);
 /* ... only its row pointers (rows + 1 int64; enqueued on `stream`, not synchronised) */
 void spasm_hip_dschur_row_pointers(const spasm_hip_dwork *W, i64 *d_Sp, void *stream);
+
+/* T = A^T on the device.  d_Tp: A->m + 1 int64; d_Tj (and d_Tx when keep_values and A->x): A->nnz int32 (A->nnz < 0: read from
+ * A->p[A->n]).  Entries of a row of T come by increasing row of A: the array the reference's spasm_transpose returns
+ * (spasm_transpose.c:5), bit for bit, whatever the launch (count, scan, fill with one position counter per column, then every
+ * column put in order by source row -- transpose.hip).  Values are carried verbatim, any int32.  A with the same (i, j) twice is
+ * outside the contract and dies ("[spasm-hip] ...") rather than return another order; so does a column index outside [0, A->m).
+ * The stream is synchronised before the return (that verdict is read back); staging buffers of A->nnz entries come from the
+ * block cache for the duration of the call.  Returns 0. */
+int spasm_hip_dtranspose(const spasm_hip_dcsr *A, int keep_values, i64 *d_Tp, int *d_Tj, spasm_ZZp *d_Tx, void *stream);
 
 /* dense rows of the Schur complement, left on the device: d_S is nrows x Sm
  * (Sm = m - rank), row-major with leading dimension ldS, values in [0, p). */

@@ -12,5 +12,6 @@ from .host import (load, compress, transpose, pivots_extract_structural, schur, 
                    empty_fact, schur_dense, ffpack_rref, ffpack_LU, echelonize, echelonize_profile, echelonize_counters, rref, kernel,
                    default_opts, gesv, solve, Solver,
                    xApy, xApy_stats, Certificate, certificate_rank_create, certificate_rank_verify, factorization_verify,
-                   DM, maximum_matching, structural_rank, dulmage_mendelsohn, strongly_connected_components, permute, dm_stats)
+                   DM, maximum_matching, structural_rank, dulmage_mendelsohn, strongly_connected_components, permute, dm_stats,
+                   kernel_basis, kernel_stats, transpose_device, transpose_stats)
 from .device import DeviceCsr, DeviceFact, SchurWorkspace, dschur                    # noqa: F401

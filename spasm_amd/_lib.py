@@ -67,6 +67,11 @@ def lib():
         "spasm_hip_echelonize_counters": (ci, [C.POINTER(C.c_longlong), ci]),
         "spasm_hip_rref": (pcsr, [plu, pint]),
         "spasm_hip_kernel": (pcsr, [plu]),
+        "spasm_hip_kernel_basis": (pcsr, [plu]),
+        "spasm_hip_kernel_stats": (ci, [C.POINTER(C.c_double), ci]),
+        "spasm_hip_dtranspose": (ci, [C.POINTER(CDcsr), ci, vp, vp, vp, vp]),
+        "spasm_hip_transpose_device": (pcsr, [pcsr, ci]),
+        "spasm_hip_transpose_stats": (ci, [C.POINTER(C.c_double), ci]),
         "spasm_hip_lu_free": (None, [plu]),
         "spasm_hip_schur_estimate_density": (C.c_double, [pcsr, pint, ci, pcsr, pint, ci]),
         "spasm_hip_schur_dense": (None, [pcsr, pint, ci, pint, plu, vp, ci, pint, pint]),

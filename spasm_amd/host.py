@@ -274,6 +274,49 @@ def kernel(F):
     return K
 
 
+def kernel_basis(F):
+    """spasm_hip_kernel_basis: the array kernel(F) returns, with the reduced rows of U, their transpose and K formed on the GPU."""
+    require_gpu("kernel_basis")
+    L = lib()
+    lu, up, qinv = _lu_for(F, 0, 0)
+    k = L.spasm_hip_kernel_basis(C.byref(lu))
+    K = copy_csr(k)
+    L.spasm_hip_csr_free(k)
+    L.spasm_hip_csr_free(up)
+    return K
+
+
+def kernel_stats():
+    """spasm_hip_kernel_stats: the last kernel_basis() call, stage by stage (ms), and its counts"""
+    out = (C.c_double * 9)()
+    lib().spasm_hip_kernel_stats(out, 9)
+    keys = ("image_ms", "reduce_ms", "transpose_ms", "assemble_ms", "download_ms", "total_ms", "nnz", "pool_retries", "rows")
+    return {k: out[t] for t, k in enumerate(keys)}
+
+
+def transpose_device(A, keep_values=True):
+    """spasm_hip_transpose_device: A^T formed on the GPU, equal to transpose(A) array for array (entries of a row by increasing
+    row of A).  A.x may be None (a pattern); the result's x is None then, and with keep_values=False."""
+    if A.p[0] != 0 or np.any(np.diff(A.p) < 0) or len(A.j) < A.nnz:
+        raise ValueError("spasm_amd.transpose_device: the row pointers of A are malformed")
+    require_gpu("transpose_device")
+    L = lib()
+    a = view_csr(A)
+    t = L.spasm_hip_transpose_device(C.byref(a), 1 if keep_values else 0)
+    out = copy_csr(t)
+    L.spasm_hip_csr_free(t)
+    return out
+
+
+def transpose_stats():
+    """spasm_hip_transpose_stats: the last device transposition: ms per stage, columns per route, the longest column, row chunks"""
+    out = (C.c_double * 9)()
+    lib().spasm_hip_transpose_stats(out, 9)
+    keys = ("upload_ms", "count_scan_ms", "fill_ms", "order_ms", "download_ms", "short_columns", "long_columns", "longest_column",
+            "row_chunks")
+    return {k: out[t] for t, k in enumerate(keys)}
+
+
 def _check_solvable(F, m, prime, what):
     if getattr(F, "L", None) is None or getattr(F, "Lp", None) is None:
         raise ValueError("spasm_amd.%s needs a factorization with L (echelonize with opts.L = True)" % what)

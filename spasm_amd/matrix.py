@@ -123,7 +123,7 @@ def view_csr(A):
     s.m = A.m
     s.p = A.p.ctypes.data_as(C.POINTER(C.c_int64))
     s.j = A.j.ctypes.data_as(C.POINTER(C.c_int))
-    s.x = A.x.ctypes.data_as(C.POINTER(C.c_int32))
+    s.x = A.x.ctypes.data_as(C.POINTER(C.c_int32)) if A.x is not None else None      # (a pattern: x set to None by the caller)
     s.field = field_of(A.prime)
     return s
 
@@ -136,8 +136,11 @@ def copy_csr(ptr):
     nnz = int(p[n])
     if nnz:
         j = np.ctypeslib.as_array(s.j, shape=(nnz,)).copy()
-        x = np.ctypeslib.as_array(s.x, shape=(nnz,)).copy()
+        x = np.ctypeslib.as_array(s.x, shape=(nnz,)).copy() if s.x else np.zeros(0, np.int32)
     else:
         j = np.zeros(0, np.int32)
         x = np.zeros(0, np.int32)
-    return Csr(n, s.m, p, j, x, s.field.p)
+    out = Csr(n, s.m, p, j, x, s.field.p)
+    if not s.x:
+        out.x = None             # a pattern: the library returned no values
+    return out
