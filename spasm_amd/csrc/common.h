@@ -47,6 +47,11 @@ inline void *xrealloc(void *old, int64_t bytes)
 
 double wtime();
 
+// A CSR matrix from outside the library, before anything reads its arrays: dies (message prefixed with who) when A is NULL,
+// has a negative dimension, or its row pointers do not start at 0 or decrease; check_columns: or a column index lies
+// outside [0, m)
+void check_host_csr(const struct spasm_csr *A, const char *who, bool check_columns = false);
+
 // Environment switches.  The SUPPORTED ones (listed in include/spasm_hip.h) are read as they are; every other SPASM_HIP_* name
 // selects an experiment, a debugging aid or a code path kept for A/B runs and tests, and is only honoured when
 // SPASM_HIP_EXPERIMENT=1 is set as well (tests/conftest.py sets it).  Returns the value or nullptr.

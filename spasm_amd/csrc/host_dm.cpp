@@ -22,23 +22,6 @@ constexpr int DM_STATS = 13;
 std::mutex dm_stats_mutex;
 double dm_last[DM_STATS];
 
-void check_pattern(const struct spasm_csr *A, const char *who)
-{
-	if (A == nullptr)
-		die("%s: A is NULL", who);
-	if (A->n < 0 || A->m < 0)
-		die("%s: A is %d x %d", who, A->n, A->m);
-	if (A->n > 0 && A->p[0] != 0)
-		die("%s: the row pointers of A start at %lld", who, (long long) A->p[0]);
-	for (int i = 0; i < A->n; i++) {
-		if (A->p[i] > A->p[i + 1])
-			die("%s: the row pointers of A decrease at row %d", who, i);
-		for (int64_t px = A->p[i]; px < A->p[i + 1]; px++)
-			if (A->j[px] < 0 || A->j[px] >= A->m)
-				die("%s: column index %d of row %d lies outside [0, %d)", who, A->j[px], i, A->m);
-	}
-}
-
 struct spasm_dm *dm_alloc(int n, int m)
 {
 	struct spasm_dm *P = (struct spasm_dm *) xmalloc(sizeof(*P));
@@ -232,7 +215,7 @@ void spasm_hip_dm_free(struct spasm_dm *P)
 int spasm_hip_maximum_matching(const struct spasm_csr *A, int *jmatch, int *imatch)
 {
 	const char *who = "spasm_hip_maximum_matching";
-	check_pattern(A, who);
+	check_host_csr(A, who, true);
 	const double t0 = wtime();
 	DmMatchStats St;
 	const int k = dm_match(A, who, jmatch, imatch, nullptr, nullptr, &St);
@@ -245,7 +228,7 @@ int spasm_hip_maximum_matching(const struct spasm_csr *A, int *jmatch, int *imat
 
 int spasm_hip_structural_rank(const struct spasm_csr *A)
 {
-	check_pattern(A, "spasm_hip_structural_rank");
+	check_host_csr(A, "spasm_hip_structural_rank", true);
 	std::vector<int> jmatch((size_t) std::max(A->n, 1)), imatch((size_t) std::max(A->m, 1));
 	return spasm_hip_maximum_matching(A, jmatch.data(), imatch.data());
 }
@@ -253,7 +236,7 @@ int spasm_hip_structural_rank(const struct spasm_csr *A)
 struct spasm_dm *spasm_hip_dulmage_mendelsohn(const struct spasm_csr *A)
 {
 	const char *who = "spasm_hip_dulmage_mendelsohn";
-	check_pattern(A, who);
+	check_host_csr(A, who, true);
 	const double t0 = wtime();
 	const int n = A->n, m = A->m;
 	std::vector<int> jmatch((size_t) std::max(n, 1)), imatch((size_t) std::max(m, 1));
@@ -276,7 +259,7 @@ struct spasm_dm *spasm_hip_dulmage_mendelsohn(const struct spasm_csr *A)
 struct spasm_dm *spasm_hip_strongly_connected_components(const struct spasm_csr *A)
 {
 	const char *who = "spasm_hip_strongly_connected_components";
-	check_pattern(A, who);
+	check_host_csr(A, who, true);
 	if (A->n != A->m)
 		die("%s: A is %d x %d, not square", who, A->n, A->m);
 	const int n = A->n;
@@ -307,7 +290,7 @@ int *spasm_hip_pinv(const int *p, int n)
 
 struct spasm_csr *spasm_hip_permute(const struct spasm_csr *A, const int *p, const int *qinv, int with_values)
 {
-	check_pattern(A, "spasm_hip_permute");
+	check_host_csr(A, "spasm_hip_permute", true);
 	const int n = A->n, m = A->m;
 	const int64_t nnz = n > 0 ? A->p[n] : 0;
 	struct spasm_csr *C = spasm_hip_csr_alloc(n, m, std::max<int64_t>(nnz, 1), A->field->p, with_values && A->x != nullptr);

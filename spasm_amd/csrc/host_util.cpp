@@ -50,6 +50,23 @@ long long *counters()
 	return c;
 }
 
+void check_host_csr(const struct spasm_csr *A, const char *who, bool check_columns)
+{
+	if (A == nullptr)
+		die("%s: A is NULL", who);
+	if (A->n < 0 || A->m < 0)
+		die("%s: A is %d x %d", who, A->n, A->m);
+	if (A->n > 0 && A->p[0] != 0)
+		die("%s: the row pointers of A start at %lld", who, (long long) A->p[0]);
+	for (int i = 0; i < A->n; i++) {
+		if (A->p[i] > A->p[i + 1])
+			die("%s: the row pointers of A decrease at row %d", who, i);
+		for (int64_t px = A->p[i]; check_columns && px < A->p[i + 1]; px++)
+			if (A->j[px] < 0 || A->j[px] >= A->m)
+				die("%s: column index %d of row %d lies outside [0, %d)", who, A->j[px], i, A->m);
+	}
+}
+
 // ---- environment switches --------------------------------------------------------------------
 // ---- a small pool of worker threads for the host planning loops ---------------------------------------------------
 // The plans of a factor image are a dozen loops of a few hundred microseconds each over 10^5 .. 10^6 rows; a std::thread per

@@ -2,7 +2,7 @@
 // the two alternating searches of the coarse Dulmage-Mendelsohn decomposition (the bfs of spasm_dm.c:22-58).
 //
 // The rows x of the smaller side are matched to their neighbours y (the pattern of A when n <= m, of its transpose otherwise:
-// the transpose is built on the device by spmv.hip's count / scan / fill).
+// the transpose is built on the device as a column-major image, colmajor.h).
 //   Greedy rounds: every free x picks its smallest free neighbour and claims it with atomicMin on x; a second kernel hands each
 //   claimed y to its smallest claimant.
 //   Augmenting phases (APFB / MS-BFS style): a level-synchronous BFS from all free x at once over alternating paths.  A level
@@ -22,9 +22,8 @@
 #include <algorithm>
 #include <vector>
 
-#include "device_types.h"
+#include "colmajor.h"
 #include "dm.h"
-#include "xa.h"
 
 namespace sh {
 
@@ -263,26 +262,19 @@ PhaseResult run_phase(const Side &G, const Search &S, hipStream_t stream, const 
 int dm_match(const struct spasm_csr *A, const char *who, int *jmatch, int *imatch, std::vector<char> *row_r1, std::vector<char> *col_c3,
              DmMatchStats *stats)
 {
-	if (A == nullptr)
-		die("%s: A is NULL", who);
+	check_host_csr(A, who);
 	if (spasm_hip_device_count() == 0)
 		die("%s: no HIP device (this library has no CPU path)", who);
-	if (A->n < 0 || A->m < 0)
-		die("%s: A is %d x %d", who, A->n, A->m);
 	const int n = A->n, m = A->m;
-	const int64_t nnz = n > 0 ? A->p[n] : 0;
-	if (n > 0 && A->p[0] != 0)
-		die("%s: the row pointers of A start at %lld", who, (long long) A->p[0]);
-	for (int i = 0; i < n; i++)
-		if (A->p[i] > A->p[i + 1])
-			die("%s: the row pointers of A decrease at row %d", who, i);
 	DmMatchStats St;
 	hipStream_t stream = 0;
 	double t0 = wtime();
 	const int nm = std::max(std::max(n, m), 1);
+	CsrUpload dA(A, false);
+	const int64_t nnz = dA.nnz;
+	int64_t *const d_Ap = dA.p;
+	int *const d_Aj = dA.j;
 	const size_t ents = (size_t) std::max<int64_t>(nnz, 1);
-	int64_t *d_Ap = (int64_t *) big_alloc((size_t) (n + 1) * 8);
-	int *d_Aj = (int *) big_alloc(ents * 4);
 	int64_t *d_Cp = (int64_t *) big_alloc((size_t) (m + 1) * 8);
 	int *d_Ci = (int *) big_alloc(ents * 4);
 	int *d_jmatch = (int *) big_alloc((size_t) std::max(n, 1) * 4);
@@ -297,17 +289,16 @@ int dm_match(const struct spasm_csr *A, const char *who, int *jmatch, int *imatc
 	S.buf0 = d_ws + 5 * (size_t) nm;
 	S.buf1 = d_ws + 6 * (size_t) nm;
 	S.ctr = d_ws + 7 * (size_t) nm;
-	if (n > 0) {
-		h2d(d_Ap, A->p, (size_t) (n + 1) * 8, stream);
-		if (nnz > 0)
-			h2d(d_Aj, A->j, (size_t) nnz * 4, stream);
-	} else {
-		HIP_CHECK(hipMemsetAsync(d_Ap, 0, 8, stream));
-	}
+	dA.send(A, stream);
 	// the column-major pattern; its count / fill counters borrow the phase workspace
-	const bool ok = xa_pattern_image(d_Ap, d_Aj, n, m, d_Cp, d_Ci, (uint32_t *) S.parent, S.ctr, stream);
-	if (!ok) {
-		for (void *q : {(void *) d_Ap, (void *) d_Aj, (void *) d_Cp, (void *) d_Ci, (void *) d_jmatch, (void *) d_imatch, (void *) d_ws})
+	HIP_CHECK(hipMemsetAsync(S.ctr, 0, 4, stream));
+	colmajor_count_scan(d_Ap, d_Aj, n, m, nnz, (uint32_t *) S.parent, S.ctr, d_Cp, stream);
+	colmajor_fill(d_Ap, d_Aj, n, m, nnz, d_Cp, (uint32_t *) S.parent, d_Ci, NoValues{}, stream);
+	HIP_CHECK(hipGetLastError());
+	int bad = 0;
+	d2h(&bad, S.ctr, sizeof(bad), stream);
+	if (bad != 0) {
+		for (void *q : {(void *) d_Cp, (void *) d_Ci, (void *) d_jmatch, (void *) d_imatch, (void *) d_ws})
 			big_free(q);
 		die("%s: a column index of A lies outside [0, %d)", who, m);
 	}
@@ -376,7 +367,7 @@ int dm_match(const struct spasm_csr *A, const char *who, int *jmatch, int *imatc
 	if (m > 0)
 		d2h(imatch, d_imatch, (size_t) m * 4, stream);
 	St.reach_ms = (wtime() - t3) * 1e3;
-	for (void *q : {(void *) d_Ap, (void *) d_Aj, (void *) d_Cp, (void *) d_Ci, (void *) d_jmatch, (void *) d_imatch, (void *) d_ws})
+	for (void *q : {(void *) d_Cp, (void *) d_Ci, (void *) d_jmatch, (void *) d_imatch, (void *) d_ws})
 		big_free(q);
 	if (stats != nullptr)
 		*stats = St;

@@ -644,14 +644,9 @@ void launch_row_scan(const int *row_len, int n, int64_t *blocksum, int64_t *Sp, 
 
 void launch_finalize(const spasm_hip_dwork *W, int nrows, hipStream_t stream)
 {
-	const int nblocks = (nrows + 1023) / 1024;
-	if (nrows == 0) {
-		HIP_CHECK(hipMemsetAsync(W->d_Sp, 0, sizeof(int64_t), stream));
+	launch_row_scan(W->d_row_len, nrows, W->d_blocksum, W->d_Sp, stream);
+	if (nrows == 0)
 		return;
-	}
-	hipLaunchKernelGGL(scan_block_sums, dim3(nblocks), dim3(256), 0, stream, W->d_row_len, nrows, W->d_blocksum);
-	hipLaunchKernelGGL(scan_of_sums, dim3(1), dim3(256), 0, stream, W->d_blocksum, nblocks);
-	hipLaunchKernelGGL(scan_finish, dim3(nblocks), dim3(256), 0, stream, W->d_row_len, nrows, W->d_blocksum, W->d_Sp);
 	int blocks = nrows < 16384 ? nrows : 16384;
 	hipLaunchKernelGGL((gather_rows_kernel<SORT_SMALL>), dim3(blocks), dim3(64), 0, stream, W->d_pool_j, W->d_pool_x,
 	                   W->d_row_off, W->d_row_len, nrows, W->d_Sp, W->d_Sj, W->d_Sx, 0, SORT_SMALL);

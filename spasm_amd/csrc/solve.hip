@@ -22,7 +22,7 @@
 #include <mutex>
 #include <numeric>
 
-#include "device_types.h"
+#include "colmajor.h"
 #include "field_dev.h"
 
 namespace sh {
@@ -245,29 +245,6 @@ __global__ void solve_row_scan_kernel(uint32_t *cnt, int nchunk, int kb, int64_t
 		run += v;
 	}
 	len[t] = run;
-}
-
-__global__ __launch_bounds__(1024) void solve_scan_kernel(const int64_t *len, int kb, int64_t *Xp)
-{
-	__shared__ int64_t s[1024];
-	int64_t carry = 0;
-	for (int base = 0; base < kb; base += 1024) {
-		const int t = base + (int) threadIdx.x;
-		s[threadIdx.x] = t < kb ? len[t] : 0;
-		__syncthreads();
-		for (int off = 1; off < 1024; off <<= 1) {
-			const int64_t v = threadIdx.x >= (unsigned) off ? s[threadIdx.x - off] : 0;
-			__syncthreads();
-			s[threadIdx.x] += v;
-			__syncthreads();
-		}
-		if (t < kb)
-			Xp[t + 1] = carry + s[threadIdx.x];
-		carry += s[1023];
-		__syncthreads();
-	}
-	if (threadIdx.x == 0)
-		Xp[0] = 0;
 }
 
 uint32_t to_mont(const Mont &M, spasm_ZZp a)
@@ -735,7 +712,7 @@ struct spasm_csr *spasm_hip_solver_gesv(spasm_hip_solver *S, const struct spasm_
 		hipLaunchKernelGGL(solve_emit_kernel<false>, dim3((nchunk + SV_WAVES - 1) / SV_WAVES, nblk), dim3(64 * SV_WAVES), 0, stream, d_Y, r,
 		                   S->d_ej, S->d_ecol, nchunk, d_cnt, nullptr, kb, nullptr, nullptr, F);
 		hipLaunchKernelGGL(solve_row_scan_kernel, dim3((kb + 255) / 256), dim3(256), 0, stream, d_cnt, nchunk, kb, d_len);
-		hipLaunchKernelGGL(solve_scan_kernel, dim3(1), dim3(1024), 0, stream, d_len, kb, d_Xp);
+		launch_pointer_scan(d_len, kb, d_Xp, stream);
 		HIP_CHECK(hipGetLastError());
 		d2h(Xp_h.data(), d_Xp, (size_t) (kb + 1) * 8, stream);
 		const int64_t nnz = Xp_h[kb];

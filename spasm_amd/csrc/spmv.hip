@@ -1,20 +1,19 @@
 // Y = X.A + Y mod p for k dense vectors X (k x n) and a CSR matrix A (n x m) -- replaces spasm_xApy (spasm_spmv.c:9-21), all k
 // vectors in one pass over A.  The products behind the rank certificates (host_cert.cpp) and the factorization checks.
 //
-// Pull form.  A is first turned into a column-major image on the device: entries counted per column, the counts scanned into
-// column pointers, the entries filled in (row index, value * 2^32 mod p) with one u32 position counter per column -- the only
-// atomics.  The order of the entries inside a column is whatever the fill produced; integer sums mod p are exact in any order,
+// Pull form.  A is first turned into a column-major image on the device (colmajor.h): row index and value * 2^32 mod p of every
+// entry.  The order of the entries inside a column is whatever the fill produced; integer sums mod p are exact in any order,
 // so the result does not depend on it.  Then every output Y[v][j] is written once, by plain stores:
 //   short columns (at most XA_LONG entries): one lane per (column, vector), the lane walks the column;
 //   long columns: one wave per column, the lanes stride the column, a wave reduction, lane 0 writes.
-// The columns are put in the two lists by a kernel that reads the column lengths the count pass produced.
+// The columns are put in the two lists by a kernel that reads the column pointers, the empty columns among the short ones.
 // Vectors are stored unknown-major on the device (X[i * k + v], Y[j * k + v]): the k lanes of one column read k adjacent words.
 // Products are montmul(x, a * 2^32) = x * a mod p in [0, p); sums are kept in 64 bits and reduced once (reduce_sum).  Any odd
 // p < 2^32.
 #include <algorithm>
 #include <mutex>
 
-#include "device_types.h"
+#include "colmajor.h"
 #include "field_dev.h"
 #include "xa.h"
 
@@ -25,92 +24,6 @@ namespace {
 constexpr int XA_LONG = 32;          // a column with more entries than this gets a whole wave
 constexpr int XA_WAVES = 4;          // waves per workgroup of the long-column kernel
 constexpr int XA_CHUNK = 4;          // vectors a lane of the long-column kernel carries at once
-
-// bit 0 of *bad: a column index outside [0, m)
-__global__ void xa_count_kernel(const int64_t *Ap, const int *Aj, int n, int m, uint32_t *cnt, int *bad)
-{
-	const int row = (int) ((blockIdx.x * (int64_t) blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
-	if (row >= n)
-		return;
-	for (int64_t px = Ap[row] + lane; px < Ap[row + 1]; px += 64) {
-		const int j = Aj[px];
-		if (j < 0 || j >= m) {
-			atomicOr(bad, 1);
-			continue;
-		}
-		atomicAdd(&cnt[j], 1u);
-	}
-}
-
-__global__ __launch_bounds__(1024) void xa_scan_kernel(const uint32_t *len, int m, int64_t *cp)
-{
-	__shared__ int64_t s[1024];
-	int64_t carry = 0;
-	for (int base = 0; base < m; base += 1024) {
-		const int t = base + (int) threadIdx.x;
-		s[threadIdx.x] = t < m ? len[t] : 0;
-		__syncthreads();
-		for (int off = 1; off < 1024; off <<= 1) {
-			const int64_t v = threadIdx.x >= (unsigned) off ? s[threadIdx.x - off] : 0;
-			__syncthreads();
-			s[threadIdx.x] += v;
-			__syncthreads();
-		}
-		if (t < m)
-			cp[t + 1] = carry + s[threadIdx.x];
-		carry += s[1023];
-		__syncthreads();
-	}
-	if (threadIdx.x == 0)
-		cp[0] = 0;
-}
-
-// the fill: entries of the columns at cp[j] + (their turn); values to a * 2^32 mod p, whatever integer the caller stored
-__global__ void xa_fill_kernel(const int64_t *Ap, const int *Aj, const int *Ax, int n, int m, const int64_t *cp, uint32_t *pos,
-                               int *ri, uint32_t *val, MontDev F)
-{
-	const int row = (int) ((blockIdx.x * (int64_t) blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
-	if (row >= n)
-		return;
-	for (int64_t px = Ap[row] + lane; px < Ap[row + 1]; px += 64) {
-		const int j = Aj[px];
-		if (j < 0 || j >= m)
-			continue;
-		const int64_t at = cp[j] + atomicAdd(&pos[j], 1u);
-		int64_t a = Ax[px];
-		if (a <= -(int64_t) F.p || a >= (int64_t) F.p) {
-			a %= (int64_t) F.p;
-		}
-		const uint32_t u = a < 0 ? (uint32_t) (a + F.p) : (uint32_t) a;
-		ri[at] = row;
-		val[at] = montmul(u, F.r2, F);        // u * 2^32 mod p
-	}
-}
-
-// the fill of a pattern-only image (xa_pattern_image): the row indices alone
-__global__ void xa_fill_pattern_kernel(const int64_t *Ap, const int *Aj, int n, int m, const int64_t *cp, uint32_t *pos, int *ri)
-{
-	const int row = (int) ((blockIdx.x * (int64_t) blockDim.x + threadIdx.x) >> 6), lane = threadIdx.x & 63;
-	if (row >= n)
-		return;
-	for (int64_t px = Ap[row] + lane; px < Ap[row + 1]; px += 64) {
-		const int j = Aj[px];
-		if (j < 0 || j >= m)
-			continue;
-		ri[cp[j] + atomicAdd(&pos[j], 1u)] = row;
-	}
-}
-
-__global__ void xa_bucket_kernel(const int64_t *cp, int m, int *short_cols, int *long_cols, int *nlist)
-{
-	const int j = blockIdx.x * blockDim.x + threadIdx.x;
-	if (j >= m)
-		return;
-	if (cp[j + 1] - cp[j] > XA_LONG)
-		long_cols[atomicAdd(&nlist[1], 1)] = j;
-	else
-		short_cols[atomicAdd(&nlist[0], 1)] = j;
-}
 
 __device__ __forceinline__ uint32_t addmod(uint32_t a, uint32_t b, const MontDev &F)
 {
@@ -193,62 +106,38 @@ struct XaPlan {
 
 XaPlan *xa_plan_create(const struct spasm_csr *A, const char *who)
 {
-	if (A == nullptr)
-		die("%s: A is NULL", who);
+	check_host_csr(A, who);
 	if (spasm_hip_device_count() == 0)
 		die("%s: no HIP device (this library has no CPU path)", who);
 	const int64_t prime = A->field->p;
 	if (prime < 3 || prime > 0xfffffffbLL || (prime & 1) == 0)
 		die("%s: modulus %lld unsupported on the GPU path", who, (long long) prime);
-	if (A->n < 0 || A->m < 0)
-		die("%s: A is %d x %d", who, A->n, A->m);
 	const int n = A->n, m = A->m;
-	const int64_t nnz = n > 0 ? A->p[n] : 0;
-	if (n > 0 && A->p[0] != 0)
-		die("%s: the row pointers of A start at %lld", who, (long long) A->p[0]);
-	for (int i = 0; i < n; i++)
-		if (A->p[i] > A->p[i + 1])
-			die("%s: the row pointers of A decrease at row %d", who, i);
+	CsrUpload dA(A, true);
+	const int64_t nnz = dA.nnz;
 	XaPlan *P = new XaPlan();
 	P->n = n;
 	P->m = m;
 	P->nnz = nnz;
 	P->prime = prime;
 	P->M = mont_setup(prime);
-	const MontDev F = to_dev(P->M);
 	hipStream_t stream = 0;
 	hipEvent_t ev[3];
 	for (auto &e : ev)
 		HIP_CHECK(hipEventCreate(&e));
-	int64_t *d_Ap = (int64_t *) big_alloc((size_t) (n + 1) * 8);
-	int *d_Aj = (int *) big_alloc((size_t) std::max<int64_t>(nnz, 1) * 4);
-	int *d_Ax = (int *) big_alloc((size_t) std::max<int64_t>(nnz, 1) * 4);
-	uint32_t *d_cnt = (uint32_t *) big_alloc((size_t) std::max(m, 1) * 4 * 2);      // counts, then the fill's positions
-	int *d_flags = (int *) big_alloc(4 * 4);                                         // bad, short count, long count
+	uint32_t *d_work = (uint32_t *) big_alloc((size_t) std::max(m, 1) * 4 * 2);     // the builder's counts and positions
+	int *d_flags = (int *) big_alloc(4 * 4);                                         // bad, short count, long count, (longest)
 	P->cp = (int64_t *) big_alloc((size_t) (m + 1) * 8);
 	P->ri = (int *) big_alloc((size_t) std::max<int64_t>(nnz, 1) * 4);
 	P->val = (uint32_t *) big_alloc((size_t) std::max<int64_t>(nnz, 1) * 4);
 	P->cols = (int *) big_alloc((size_t) std::max(m, 1) * 4 * 2);
 	HIP_CHECK(hipEventRecord(ev[0], stream));
-	if (n > 0) {
-		h2d(d_Ap, A->p, (size_t) (n + 1) * 8, stream);
-		if (nnz > 0) {
-			h2d(d_Aj, A->j, (size_t) nnz * 4, stream);
-			h2d(d_Ax, A->x, (size_t) nnz * 4, stream);
-		}
-	}
+	dA.send(A, stream);
 	HIP_CHECK(hipEventRecord(ev[1], stream));
-	HIP_CHECK(hipMemsetAsync(d_cnt, 0, (size_t) std::max(m, 1) * 4 * 2, stream));
 	HIP_CHECK(hipMemsetAsync(d_flags, 0, 4 * 4, stream));
-	const unsigned row_blocks = (unsigned) (((int64_t) n * 64 + 255) / 256);
-	if (n > 0 && m > 0)
-		hipLaunchKernelGGL(xa_count_kernel, dim3(row_blocks), dim3(256), 0, stream, d_Ap, d_Aj, n, m, d_cnt, d_flags);
-	hipLaunchKernelGGL(xa_scan_kernel, dim3(1), dim3(1024), 0, stream, d_cnt, m, P->cp);
-	if (n > 0 && m > 0)
-		hipLaunchKernelGGL(xa_fill_kernel, dim3(row_blocks), dim3(256), 0, stream, d_Ap, d_Aj, d_Ax, n, m, P->cp, d_cnt + std::max(m, 1),
-		                   P->ri, P->val, F);
-	if (m > 0)
-		hipLaunchKernelGGL(xa_bucket_kernel, dim3((m + 255) / 256), dim3(256), 0, stream, P->cp, m, P->cols, P->cols + m, d_flags + 1);
+	colmajor_count_scan(dA.p, dA.j, n, m, nnz, d_work, d_flags, P->cp, stream);
+	colmajor_fill(dA.p, dA.j, n, m, nnz, P->cp, d_work, P->ri, MontValues{dA.x, P->val, to_dev(P->M)}, stream);
+	colmajor_bucket(P->cp, m, XA_LONG, true, P->cols, P->cols + m, d_flags + 1, stream);
 	HIP_CHECK(hipGetLastError());
 	HIP_CHECK(hipEventRecord(ev[2], stream));
 	int flags[4];
@@ -258,10 +147,7 @@ XaPlan *xa_plan_create(const struct spasm_csr *A, const char *who)
 	HIP_CHECK(hipEventElapsedTime(&e12, ev[1], ev[2]));
 	for (auto &e : ev)
 		HIP_CHECK(hipEventDestroy(e));
-	big_free(d_Ap);
-	big_free(d_Aj);
-	big_free(d_Ax);
-	big_free(d_cnt);
+	big_free(d_work);
 	big_free(d_flags);
 	if (flags[0] != 0) {
 		xa_plan_destroy(P);
@@ -274,25 +160,6 @@ XaPlan *xa_plan_create(const struct spasm_csr *A, const char *who)
 	P->upload_ms = e01;
 	P->build_ms = e12;
 	return P;
-}
-
-// the pattern of A column by column, for the matching (matching.hip): the same count and scan as the plan, a fill without values
-bool xa_pattern_image(const int64_t *d_Ap, const int *d_Aj, int n, int m, int64_t *d_cp, int *d_ri, uint32_t *d_work, int *d_bad,
-                      hipStream_t stream)
-{
-	HIP_CHECK(hipMemsetAsync(d_work, 0, (size_t) std::max(m, 1) * 4 * 2, stream));
-	HIP_CHECK(hipMemsetAsync(d_bad, 0, 4, stream));
-	const unsigned row_blocks = (unsigned) (((int64_t) n * 64 + 255) / 256);
-	if (n > 0 && m > 0)
-		hipLaunchKernelGGL(xa_count_kernel, dim3(row_blocks), dim3(256), 0, stream, d_Ap, d_Aj, n, m, d_work, d_bad);
-	hipLaunchKernelGGL(xa_scan_kernel, dim3(1), dim3(1024), 0, stream, d_work, m, d_cp);
-	if (n > 0 && m > 0)
-		hipLaunchKernelGGL(xa_fill_pattern_kernel, dim3(row_blocks), dim3(256), 0, stream, d_Ap, d_Aj, n, m, d_cp, d_work + std::max(m, 1),
-		                   d_ri);
-	HIP_CHECK(hipGetLastError());
-	int bad = 0;
-	d2h(&bad, d_bad, sizeof(bad), stream);
-	return bad == 0;
 }
 
 void xa_plan_destroy(XaPlan *P)

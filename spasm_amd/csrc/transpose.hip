@@ -1,10 +1,9 @@
 // T = A^T for a CSR matrix resident on the device, in the STABLE order: the entries of a row of T come by increasing row of A --
 // the array spasm_transpose (spasm_transpose.c:5) and spasm_hip_transpose (host_util.cpp) return, bit for bit, whatever the launch.
 //
-// Count, scan, fill, order.  The entries are counted per column (u32 atomics), the counts scanned into Tp by one workgroup, and
-// every entry is dropped into the slice of its column of a staging copy at (its turn): one u32 position counter per column, the
-// only other atomics -- the order inside a slice is whatever the fill produced.  Then every slice is put in order by source row
-// on its way from the staging copy to T, each entry moved once:
+// Count, scan, fill, order.  The first three are the column-major image of colmajor.h, built into a staging copy: the order
+// inside the slice of a column is whatever the fill produced.  Then every slice is put in order by source row on its way from
+// the staging copy to T, each entry moved once:
 //   short slices (at most tr_short() entries): one wave per slice.  The keys go to LDS; every lane ranks its keys by counting the
 //     smaller ones (broadcast reads, four keys per read).  A key that meets its own value twice is a repeated (i, j).
 //   long slices: one workgroup per slice.  The keys of a slice are DISTINCT row indices in [0, n): the slice sets its bits in a
@@ -19,7 +18,7 @@
 #include <climits>
 #include <mutex>
 
-#include "device_types.h"
+#include "colmajor.h"
 
 namespace sh {
 
@@ -29,10 +28,10 @@ constexpr int TR_SHORT_DEFAULT = 256;        // slices up to this length take th
 constexpr int TR_SHORT_MAX = 1024;           // ... at most: 4 KB of keys per wave
 constexpr int TR_CHUNK_MAX = 262144;         // rows per bitmap chunk (SPASM_HIP_TRANSPOSE_CHUNK): 32 KB of bits + 16 KB of offsets
 constexpr int TR_WAVES = 4;                  // waves per workgroup of the short route
-constexpr int TR_MAX_BLOCKS = 1 << 20;       // row-parallel kernels: grid-stride beyond this many workgroups
 
 enum { TR_BAD = 0, TR_NSHORT, TR_NLONG, TR_LONGEST, TR_INFO };      // the words of d_info; TR_BAD bit 0: column index outside
-                                                                  // [0, m), bit 1: a repeated (i, j)
+                                                                  // [0, m), bit 1: a repeated (i, j); the next three in the
+                                                                  // order of colmajor_bucket's counters
 
 int tr_short()
 {
@@ -43,79 +42,6 @@ int tr_chunk()
 {
 	const int c = std::max(32, std::min(TR_CHUNK_MAX, env_int("SPASM_HIP_TRANSPOSE_CHUNK", TR_CHUNK_MAX)));
 	return (c + 31) & ~31;
-}
-
-__global__ __launch_bounds__(256) void tr_count_kernel(const int64_t *Ap, const int *Aj, int n, int m, uint32_t *cnt, int *info)
-{
-	const int lane = threadIdx.x & 63;
-	const int64_t waves = (int64_t) gridDim.x * 4;
-	for (int64_t row = (int64_t) blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += waves)
-		for (int64_t px = Ap[row] + lane; px < Ap[row + 1]; px += 64) {
-			const int j = Aj[px];
-			if (j < 0 || j >= m) {
-				atomicOr(&info[TR_BAD], 1);
-				continue;
-			}
-			atomicAdd(&cnt[j], 1u);
-		}
-}
-
-// one workgroup: Tp[0] = 0, Tp[j + 1] = len[0] + ... + len[j]
-__global__ __launch_bounds__(1024) void tr_scan_kernel(const uint32_t *len, int m, int64_t *Tp)
-{
-	__shared__ int64_t s[1024];
-	int64_t carry = 0;
-	for (int base = 0; base < m; base += 1024) {
-		const int t = base + (int) threadIdx.x;
-		s[threadIdx.x] = t < m ? len[t] : 0;
-		__syncthreads();
-		for (int off = 1; off < 1024; off <<= 1) {
-			const int64_t v = threadIdx.x >= (unsigned) off ? s[threadIdx.x - off] : 0;
-			__syncthreads();
-			s[threadIdx.x] += v;
-			__syncthreads();
-		}
-		if (t < m)
-			Tp[t + 1] = carry + s[threadIdx.x];
-		carry += s[1023];
-		__syncthreads();
-	}
-	if (threadIdx.x == 0)
-		Tp[0] = 0;
-}
-
-// the fill: (row, value) of every entry into the slice of its column of the staging copy, at its turn
-__global__ __launch_bounds__(256) void tr_fill_kernel(const int64_t *Ap, const int *Aj, const int *Ax, int n, int m, const int64_t *Tp,
-                                                      uint32_t *pos, int *sj, int *sx)
-{
-	const int lane = threadIdx.x & 63;
-	const int64_t waves = (int64_t) gridDim.x * 4;
-	for (int64_t row = (int64_t) blockIdx.x * 4 + (threadIdx.x >> 6); row < n; row += waves)
-		for (int64_t px = Ap[row] + lane; px < Ap[row + 1]; px += 64) {
-			const int j = Aj[px];
-			if (j < 0 || j >= m)
-				continue;
-			const int64_t at = Tp[j] + atomicAdd(&pos[j], 1u);
-			sj[at] = (int) row;
-			if (sx != nullptr)
-				sx[at] = Ax[px];
-		}
-}
-
-// the non-empty columns in two lists (in no particular order: nothing depends on it), and the longest one
-__global__ void tr_bucket_kernel(const int64_t *Tp, int m, int short_max, int *short_cols, int *long_cols, int *info)
-{
-	const int j = blockIdx.x * blockDim.x + threadIdx.x;
-	if (j >= m)
-		return;
-	const int64_t len = Tp[j + 1] - Tp[j];
-	if (len == 0)
-		return;
-	atomicMax(&info[TR_LONGEST], (int) len);
-	if (len > short_max)
-		long_cols[atomicAdd(&info[TR_NLONG], 1)] = j;
-	else
-		short_cols[atomicAdd(&info[TR_NSHORT], 1)] = j;
 }
 
 // short route: one wave per slice of at most short_max <= L4 entries; L4 keys of LDS per wave, L4 a multiple of 4
@@ -224,11 +150,6 @@ __global__ __launch_bounds__(256) void tr_long_kernel(const int *cols, const int
 std::mutex tr_stats_mutex;
 double tr_last[9];
 
-unsigned row_blocks(int n)
-{
-	return (unsigned) std::max<int64_t>(1, std::min<int64_t>(TR_MAX_BLOCKS, ((int64_t) n + 3) / 4));
-}
-
 }  // namespace
 
 // the device part: everything on `stream`, which is synchronised before the return (the route lists and the verdict on the input
@@ -252,7 +173,7 @@ void dtranspose_run(const spasm_hip_dcsr *A, int keep_values, int64_t *d_Tp, int
 		die("%s: values asked for and no array to put them in", who);
 	const int short_max = tr_short(), chunk = tr_chunk();
 	const int mm = std::max(m, 1);
-	uint32_t *d_cnt = (uint32_t *) big_alloc((size_t) mm * 4 * 2);                    // counts, then the fill's positions
+	uint32_t *d_work = (uint32_t *) big_alloc((size_t) mm * 4 * 2);                   // the builder's counts and positions
 	int *d_info = (int *) big_alloc(TR_INFO * 4);
 	int *d_cols = (int *) big_alloc((size_t) mm * 4 * 2);                           // short list, long list
 	int *d_sj = (int *) big_alloc((size_t) std::max<int64_t>(nnz, 1) * 4);
@@ -261,18 +182,15 @@ void dtranspose_run(const spasm_hip_dcsr *A, int keep_values, int64_t *d_Tp, int
 	for (auto &e : ev)
 		HIP_CHECK(hipEventCreate(&e));
 	HIP_CHECK(hipEventRecord(ev[0], stream));
-	HIP_CHECK(hipMemsetAsync(d_cnt, 0, (size_t) mm * 4 * 2, stream));
 	HIP_CHECK(hipMemsetAsync(d_info, 0, TR_INFO * 4, stream));
-	if (n > 0 && m > 0 && nnz > 0)
-		hipLaunchKernelGGL(tr_count_kernel, dim3(row_blocks(n)), dim3(256), 0, stream, A->p, A->j, n, m, d_cnt, d_info);
-	hipLaunchKernelGGL(tr_scan_kernel, dim3(1), dim3(1024), 0, stream, d_cnt, m, d_Tp);
+	colmajor_count_scan(A->p, A->j, n, m, nnz, d_work, d_info + TR_BAD, d_Tp, stream);
 	HIP_CHECK(hipEventRecord(ev[1], stream));
-	if (n > 0 && m > 0 && nnz > 0)
-		hipLaunchKernelGGL(tr_fill_kernel, dim3(row_blocks(n)), dim3(256), 0, stream, A->p, A->j, vals ? A->x : nullptr, n, m, d_Tp, d_cnt + mm,
-		                   d_sj, d_sx);
+	if (vals)
+		colmajor_fill(A->p, A->j, n, m, nnz, d_Tp, d_work, d_sj, RawValues{A->x, d_sx}, stream);
+	else
+		colmajor_fill(A->p, A->j, n, m, nnz, d_Tp, d_work, d_sj, NoValues{}, stream);
 	HIP_CHECK(hipEventRecord(ev[2], stream));
-	if (m > 0)
-		hipLaunchKernelGGL(tr_bucket_kernel, dim3((m + 255) / 256), dim3(256), 0, stream, d_Tp, m, short_max, d_cols, d_cols + mm, d_info);
+	colmajor_bucket(d_Tp, m, short_max, false, d_cols, d_cols + mm, d_info + TR_NSHORT, stream);
 	HIP_CHECK(hipGetLastError());
 	int info[TR_INFO];
 	d2h(info, d_info, sizeof(info), stream);
@@ -296,7 +214,7 @@ void dtranspose_run(const spasm_hip_dcsr *A, int keep_values, int64_t *d_Tp, int
 	HIP_CHECK(hipEventElapsedTime(&e23, ev[2], ev[3]));
 	for (auto &e : ev)
 		HIP_CHECK(hipEventDestroy(e));
-	big_free(d_cnt);
+	big_free(d_work);
 	big_free(d_info);
 	big_free(d_cols);
 	big_free(d_sj);
@@ -345,38 +263,23 @@ int spasm_hip_dtranspose(const spasm_hip_dcsr *A, int keep_values, i64 *d_Tp, in
 struct spasm_csr *spasm_hip_transpose_device(const struct spasm_csr *A, int keep_values)
 {
 	const char *who = "spasm_hip_transpose_device";
-	if (A == nullptr)
-		die("%s: A is NULL", who);
+	check_host_csr(A, who);
 	if (spasm_hip_device_count() == 0)
 		die("%s: no HIP device (this library has no CPU path)", who);
 	const int n = A->n, m = A->m;
-	if (n < 0 || m < 0)
-		die("%s: A is %d x %d", who, n, m);
-	if (A->p[0] != 0)
-		die("%s: the row pointers of A start at %lld", who, (long long) A->p[0]);
-	for (int i = 0; i < n; i++)
-		if (A->p[i] > A->p[i + 1])
-			die("%s: the row pointers of A decrease at row %d", who, i);
-	const i64 nnz = A->p[n];
 	const bool vals = keep_values != 0 && A->x != nullptr;
 	hipStream_t stream = 0;
+	CsrUpload up(A, vals);
+	const i64 nnz = up.nnz;
 	const size_t entries = (size_t) std::max<i64>(nnz, 1) * 4;
-	i64 *d_Ap = (i64 *) big_alloc((size_t) (n + 1) * 8);
-	int *d_Aj = (int *) big_alloc(entries);
-	int *d_Ax = vals ? (int *) big_alloc(entries) : nullptr;
 	i64 *d_Tp = (i64 *) big_alloc((size_t) (m + 1) * 8);
 	int *d_Tj = (int *) big_alloc(entries);
 	int *d_Tx = vals ? (int *) big_alloc(entries) : nullptr;
 	const double t0 = wtime();
-	h2d(d_Ap, A->p, (size_t) (n + 1) * 8, stream);
-	if (nnz > 0) {
-		h2d(d_Aj, A->j, (size_t) nnz * 4, stream);
-		if (vals)
-			h2d(d_Ax, A->x, (size_t) nnz * 4, stream);
-	}
+	up.send(A, stream);
 	HIP_CHECK(hipStreamSynchronize(stream));
 	const double t1 = wtime();
-	const spasm_hip_dcsr dA{n, m, nnz, d_Ap, d_Aj, d_Ax};
+	const spasm_hip_dcsr dA{n, m, nnz, up.p, up.j, up.x};
 	double ms[3], counts[4];
 	dtranspose_run(&dA, keep_values, d_Tp, d_Tj, d_Tx, stream, who, ms, counts);
 	const double t2 = wtime();
@@ -388,9 +291,10 @@ struct spasm_csr *spasm_hip_transpose_device(const struct spasm_csr *A, int keep
 			d2h(T->x, d_Tx, (size_t) nnz * 4, stream);
 	}
 	transpose_record((t1 - t0) * 1e3, ms, (wtime() - t2) * 1e3, counts);
-	for (void *q : {(void *) d_Ap, (void *) d_Aj, (void *) d_Ax, (void *) d_Tp, (void *) d_Tj, (void *) d_Tx})
-		if (q != nullptr)
-			big_free(q);
+	big_free(d_Tp);
+	big_free(d_Tj);
+	if (d_Tx != nullptr)
+		big_free(d_Tx);
 	return T;
 }
 

@@ -106,12 +106,42 @@ def transpose_cases():
     return out
 
 
-# ---- kernel bases ----
 def _mulmod(a, b, p):
     """a * b mod p entry by entry, exact: int64 where the product fits, Python integers (object arrays) otherwise"""
     if (p - 1) * (p - 1) < 2 ** 63:
         return a * b % p
     return np.asarray(a.astype(object) * b.astype(object) % p, object).astype(np.int64)
+
+
+# ---- the column-major image through its other users (tests/test_gpu_colmajor.py) ----
+COLMAJOR_MODULI = [42013, 4294967291]
+XA_LONG = 32             # spmv.hip: a column with more entries goes to the long list of x.A
+
+
+def with_prime(A, p):
+    """the same arrays as a matrix mod p"""
+    return spasm_amd.Csr(A.n, A.m, A.p, A.j, A.x, p)
+
+
+def model_xApy(X, A, Y0):
+    """Y0 + X.A mod A.prime as residues in [0, p), exact, entry by entry: every product is reduced before it is added, and a
+    column adds up fewer than 2^31 terms below 2^32"""
+    p = A.prime
+    rows = np.repeat(np.arange(A.n), np.diff(A.p))
+    vals = np.asarray(A.x[:A.nnz], np.int64) % p
+    prod = _mulmod(np.asarray(X, np.int64)[:, rows] % p, vals[None, :], p)
+    out = (np.asarray(Y0, np.int64) % p).T.copy()
+    np.add.at(out, A.j[:A.nnz], prod.T)
+    return (out % p).T
+
+
+def xa_inputs(A, k, seed):
+    """seeded X (k x n) and Y0 (k x m) of residues"""
+    rng = np.random.default_rng(seed)
+    return rng.integers(0, A.prime, (k, A.n), dtype=np.int64), rng.integers(0, A.prime, (k, A.m), dtype=np.int64)
+
+
+# ---- kernel bases ----
 
 
 def dense(A, p):

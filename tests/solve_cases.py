@@ -21,11 +21,13 @@ SOURCE_EXPRESSIONS = [
     "constexpr int SV_WAVES = 4;", "constexpr int SV_TAIL_WAVES = 16;", "constexpr int SV_THIN = 16;", "constexpr int SV_RUN = 2;",
     "constexpr int SV_SPLIT = 64;",
     "S.lptr[e + 1] - S.lptr[e] <= SV_THIN", "if (e - l < SV_RUN)", "deps >= SV_SPLIT * nodes",
-    "for (int base = 0; base < kb; base += 1024)", "__shared__ int64_t s[1024];",
+    "launch_pointer_scan(d_len, kb, d_Xp, stream);",
     "std::max(1, std::min(256, S->r / 512))", "std::max(1, std::min(512, (nc + 7) / 8))",
     "for (; d + 4 <= e; d += 4)", "n * w / SV_TAIL_WAVES", "n * (w + 1) / SV_TAIL_WAVES",
     "(s < v || s >= F.p)", "env_int(\"SPASM_HIP_SOLVE_BATCH\", 0)",
 ]
+# ... and of the scan of the row lengths, which the emit path shares with the column-major images (colmajor.hip)
+SCAN_EXPRESSIONS = ["for (int base = 0; base < n; base += 1024)", "__shared__ int64_t s[1024];"]
 SMALL_PRIMES = [3, 42013, 65537, 4294967291]
 
 

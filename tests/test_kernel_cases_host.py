@@ -54,6 +54,25 @@ def test_the_two_default_thresholds_the_cases_are_built_around():
         assert expr in text, expr
 
 
+@pytest.mark.parametrize("p", kc.COLMAJOR_MODULI)
+@pytest.mark.parametrize("case", TRANSPOSE_CASES, ids=[c[0] for c in TRANSPOSE_CASES])
+def test_model_xApy_is_the_dense_product(case, p):
+    """the entry-by-entry model tests/test_gpu_colmajor.py holds x.A against, checked against the dense helpers"""
+    A = kc.with_prime(case[1], p)
+    X, Y0 = kc.xa_inputs(A, 3, 7)
+    want = (kc.matmul_mod(X, kc.dense(A, p), p) + Y0) % p
+    assert np.array_equal(kc.model_xApy(X, A, Y0), want)
+    assert np.array_equal(kc.model_xApy(X[:1], A, Y0[:1]), want[:1])
+
+
+def test_colmajor_cases_reach_both_lists_of_xA_and_a_scan_carry():
+    lens = {c[0]: np.diff(kc.model_transpose(c[1])[0]) for c in TRANSPOSE_CASES}
+    assert "XA_LONG = %d;" % kc.XA_LONG in open(os.path.join(ROOT, "spasm_amd", "csrc", "spmv.hip")).read()
+    assert lens["one_column_4097_rows"].tolist() == [4097] and lens["one_row_4097_columns"].tolist() == [1] * 4097
+    assert np.sum(lens["random_sparse"] == 0) > 0 and np.sum(lens["full_alternating_last"] > kc.XA_LONG) == 2
+    assert [int(lens["one_column_%d_rows" % n][0] > kc.XA_LONG) for n in (1, 63, 64, 65)] == [0, 1, 1, 1]
+
+
 @pytest.mark.parametrize("case", FACTOR_CASES, ids=[c[0] for c in FACTOR_CASES])
 def test_model_kernel_of_the_constructed_factors(case):
     """U . K^T == 0 and rank K == m - r for the exact model, and the factor is what the library expects: unit pivots first,

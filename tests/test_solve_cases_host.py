@@ -1,5 +1,5 @@
 """CPU checks of tests/solve_cases.py: the model returns what the compiled reference stored for every case of
-tests/golden/reference/gesv.npz, the constants and expressions the shapes are built around are still in solve.hip, and
+tests/golden/reference/gesv.npz, the constants and expressions the shapes are built around are still in solve.hip (the scan: colmajor.hip), and
 every shape of tests/test_gpu_solve_shapes.py lands on the launches it claims."""
 import os
 
@@ -29,6 +29,12 @@ def test_source_expression_is_still_there(expr):
     """a moved or changed constant fails here first: update solve_cases.py (and the shapes built on it) with it"""
     with open(SOLVE_HIP) as f:
         assert expr in f.read(), "`%s` no longer in spasm_amd/csrc/solve.hip" % expr
+
+
+@pytest.mark.parametrize("expr", sc.SCAN_EXPRESSIONS)
+def test_scan_expression_is_still_there(expr):
+    with open(os.path.join(os.path.dirname(SOLVE_HIP), "colmajor.hip")) as f:
+        assert expr in f.read(), "`%s` no longer in spasm_amd/csrc/colmajor.hip" % expr
 
 
 def test_python_constants_are_the_sources():
