@@ -45,9 +45,8 @@ constexpr int BS_RING = 768;       // rows per chunk (the LDS ring holds RING ro
 constexpr int BS_NEARCAP = 1024;   // dependencies inside a chunk that do not fit the pass table (rows with more than two)
 constexpr int BS_PASSCAP = 80;     // phase-B passes of a chunk (32 rows of one level each)
 constexpr int BS_PASSROWS = 32;
-// an empty slot of the pass table points at a spare row of the ring (index BS_RING) with coefficient 0: the signed kernels
-// run every lane through the same reads, multiply-adds and write, without a branch
-#define BS_EMPTY_ENTRY uint4{(uint32_t) BS_RING, (uint32_t) BS_RING | ((uint32_t) BS_RING << 16), 0u, 0u}
+// an empty slot of the pass table points at a spare row of the ring (row BS_RING, i.e. word offset RING * RSTR: bs_pass_empty)
+// with coefficient 0: the signed kernels run every lane through the same reads, multiply-adds and write, without a branch
 constexpr uint32_t BS_NONE = 0xFFFFFFFFu;
 
 template <typename T> T *dalloc(int64_t count)
@@ -188,11 +187,41 @@ template <int HI, bool FIRST> __device__ __forceinline__ void sgn_mad_half(uint3
 	}
 }
 
+// ---- the table of phase-B passes: one 16-byte entry per row slot of a pass ------------------------------
+// Rows of the ring are OFFSETS in words, slot * RSTR (RSTR = BsGeom::RSTR of the kernel the plan was cut for; (RING + 1) * RSTR
+// fits 16 bits for every shape, backsolve_plan checks it): an LDS address is one v_mad_u32_u16 that picks its half of the word.
+//   ordinary row (one or two dependencies inside the chunk):
+//     .x = own offset, .y = offset of dependency 0 | offset of dependency 1 << 16 (one dependency: the same row again),
+//     p < 2^16 (PLAIN): .z = coefficient 0 | coefficient 1 << 16 (as bs_head: v_mad_i32_i16 takes either half), .w = 0;
+//     otherwise:        .z = coefficient 0, .w = coefficient 1 (Montgomery form);
+//   long row (more than two): .x = own offset | number of dependencies << 16, .y = offset of dependency 0, .z = coefficient 0,
+//     .w = where the others start in the chunk's list (`near`: {offset, coefficient}).
+// Long rows sit in passes of their own, after the ordinary passes of their level (the order inside a level is free).  The
+// kernel never looks for them: the chunk descriptor says how many ordinary passes come before the first long pass, and the
+// high half of .y of EVERY slot of a long pass how many ordinary passes follow it before the next one.
+// An empty slot is the spare row with coefficient 0.
+__host__ __device__ __forceinline__ uint4 bs_pass_empty(uint32_t spare_off)
+{
+	return uint4{spare_off, spare_off | (spare_off << 16), 0u, 0u};
+}
+
+// byte address in LDS of the word `base` (a byte address) + 4 * the low (HI = 0) or high (HI = 1) half of `packed`
+template <int HI> __device__ __forceinline__ uint32_t bs_ring_at(uint32_t packed, uint32_t base)
+{
+	uint32_t a;
+	if constexpr (HI == 0)
+		asm("v_mad_u32_u16 %0, %1, 4, %2" : "=v"(a) : "v"(packed), "v"(base));
+	else
+		asm("v_mad_u32_u16 %0, %1, 4, %2 op_sel:[1,0,0,0]" : "=v"(a) : "v"(packed), "v"(base));
+	return a;
+}
+using bs_lds_word = __attribute__((address_space(3))) uint32_t;
+
 // LPR lanes (words) per row of a slab: a row of a slab is LPR * 4 bytes (128 B with LPR = 32: whole cache lines, half
 // as many requests as 64-byte segments -- the kernel is bound by the rate of such requests).
 // NW waves per workgroup; a wave instruction covers 64 / LPR rows.
 // RING / PASSROWS / PASSCAP: rows per chunk, rows per phase-B pass, passes per chunk -- the plan (backsolve_plan) is built
-// for the values of the kernel that will run it (BsImage::ring, passrows, passcap).
+// for the values of the kernel that will run it, and for its RSTR (BsImage::ring, passrows, passcap, rstr).
 template <bool PACKED, int LPR, int NW, int RING = BS_RING, int PASSROWS = BS_PASSROWS, int PASSCAP = BS_PASSCAP> struct BsGeom {
 	static constexpr int RING_ = RING, PASSROWS_ = PASSROWS, PASSCAP_ = PASSCAP;
 	static constexpr int THREADS = 64 * NW;
@@ -218,8 +247,6 @@ template <bool PACKED, int LPR, int NW, int RING = BS_RING, int PASSROWS = BS_PA
 template <bool PACKED, bool PLAIN, int LPR, int NW, bool SGN = false, int RING = BS_RING, int PASSROWS = BS_PASSROWS, int PASSCAP = BS_PASSCAP, int WGS_PER_CU = 1>
 __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b)
 {
-	// an empty slot of the pass table points at the spare row of the ring (index RING) with coefficient 0
-	const uint4 EMPTY_ENTRY = uint4{(uint32_t) RING, (uint32_t) RING | ((uint32_t) RING << 16), 0u, 0u};
 	static_assert(!SGN || (PACKED && PLAIN), "signed entries are packed 16-bit entries");
 	const uint32_t bm = PLAIN ? (uint32_t) (0x100000000ull / b.F.p) : 0u;
 	const SgnDev G = b.G;
@@ -240,11 +267,11 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 	auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 	const int rs = lane / LPR, wl = lane % LPR;           // row slot of the lane, its word inside the row (phases A and C)
 	constexpr int RSTR = Geo::RSTR;                        // words between two rows of the ring
+	constexpr uint32_t SPARE = (uint32_t) (RING * RSTR);   // the spare row (row RING), where the empty slots of the pass table point
 	// phase B splits the COLUMNS among the waves: a wave owns WPW words of every row, a wave instruction covers RSB rows
 	constexpr int WPW = LPR / NW, RSB = 64 / WPW;
 	static_assert(WPW >= 1 && LPR % NW == 0 && 64 % WPW == 0, "every wave takes the same number of words of a row through phase B");
 	static_assert(PASSROWS % RSB == 0, "a pass is a whole number of wave instructions");
-	const int rsb = lane / WPW, wlb = wave * WPW + lane % WPW;
 	const MontDev F = b.F;
 	const int64_t ldw = b.ldR / Word<PACKED>::CPL;       // row stride of R in words
 	uint32_t *Rs = static_cast<uint32_t *>(b.R) + (int64_t) blockIdx.x * LPR + wl;
@@ -283,11 +310,15 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 			const uint4 v = b.far_head[(t < c.hi - c.lo) ? c.lo + t : 0];
 			m_fh.template at<q>() = (t < c.hi - c.lo) ? v : bs_head<PLAIN>(BS_NONE, 0u, BS_NONE, 0u);
 		});
+		// (the addresses of these loads are formed here, chunk by chunk, from a thread id the compiler cannot see through: formed
+		//  once before the loop of the chunks they are 64-bit values kept through phase A, which has no registers to spare)
+		int tid_m = tid;
+		asm volatile("" : "+v"(tid_m));
 		bs_static_for<0, Geo::N_PTAB>([&](auto qq) {
 			constexpr int q = decltype(qq)::value;
-			const int t = tid + q * Geo::THREADS;
+			const int t = tid_m + q * Geo::THREADS;
 			const uint4 v = b.ptab[(t < c.npass * PASSROWS) ? (int64_t) c.pass0 * PASSROWS + t : 0];
-			m_ptab.template at<q>() = (t < c.npass * PASSROWS) ? v : uint4{(uint32_t) RING, (uint32_t) RING | ((uint32_t) RING << 16), 0u, 0u};
+			m_ptab.template at<q>() = (t < c.npass * PASSROWS) ? v : bs_pass_empty(SPARE);
 		});
 	};
 	auto store_meta = [&]() {
@@ -325,7 +356,8 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 		c.lo = __builtin_amdgcn_readfirstlane((int) raw_a.x);
 		c.hi = __builtin_amdgcn_readfirstlane((int) raw_a.y);
 		c.pass0 = __builtin_amdgcn_readfirstlane((int) raw_a.z);
-		c.npass = __builtin_amdgcn_readfirstlane((int) raw_a.w);
+		c.npass = (unsigned short) __builtin_amdgcn_readfirstlane((int) (raw_a.w & 0xFFFFu));
+		c.nord = (unsigned short) __builtin_amdgcn_readfirstlane((int) (raw_a.w >> 16));
 		c.near0 = __builtin_amdgcn_readfirstlane((int) raw_b.x);
 		c.nnear = __builtin_amdgcn_readfirstlane((int) raw_b.y);
 		c.np0 = __builtin_amdgcn_readfirstlane((int) raw_b.z);
@@ -532,98 +564,104 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 		// ---- phase B: the chain of levels, in LDS ----
 		// Columns never meet in a triangular solve, so every wave takes ITS columns (WPW words of every row) through all the
 		// levels of the chunk on its own: no barrier between the levels -- the LDS serves a wave's reads and writes in
-		// order.  The rows come as a flat table of passes (32 rows of one level each, levels in order): one 16-byte entry
-		// holds everything a row with one or two dependencies inside the chunk needs, and the entry of the next trip is
-		// in flight during the arithmetic of this one.  (Every wave decodes every entry: the table is what keeps that cheap.)
+		// order.  The rows come as a flat table of passes (PASSROWS rows of one level each, levels in order): one 16-byte entry
+		// (layout: bs_pass_empty above) holds everything a row with one or two dependencies inside the chunk needs, ring
+		// offsets ready and scaled, and the entry of the next trip is in flight during the arithmetic of this one.  (Every wave
+		// decodes every entry: the table is what keeps that cheap.)  The ordinary pass knows nothing of rows with more than
+		// two dependencies: those have passes of their own, and the table says where (runs of ordinary passes between them).
 		{
-			const int niter = ch.npass * (PASSROWS / RSB);
-			uint4 e = (niter > 0) ? ptab[rsb] : EMPTY_ENTRY;
-			for (int it = 0; it < niter; it++) {
-				const uint4 e_next = (it + 1 < niter) ? ptab[(it + 1) * RSB + rsb] : EMPTY_ENTRY;
-				const int cnt = (int) (e.x >> 16);                    // cnt != 0: this lane has a row in the pass
+			constexpr int IPP = PASSROWS / RSB;          // wave instructions (trips) per pass
+			const int niter = ch.npass * IPP;
+			// the lane's row slot of a trip and its word of a row, worked out here, from a thread id the compiler cannot see through:
+			// what hangs on them would otherwise be kept in registers through phase A, which has none to spare
+			int tid_b = tid;
+			asm volatile("" : "+v"(tid_b));
+			const int rsb = (tid_b & 63) / WPW, wlb = (tid_b >> 6) * WPW + (tid_b & 63) % WPW;
+			const uint4 *pe = ptab + rsb;
+			// byte address in LDS of this lane's word of row 0 of the ring: the entries' offsets are added to it
+			const uint32_t wlb_at = (uint32_t) (uintptr_t) (bs_lds_word *) (ring + wlb);
+			auto word = [&](uint32_t at) -> bs_lds_word & { return *reinterpret_cast<bs_lds_word *>((uintptr_t) at); };
+			auto ordinary = [&](const uint4 e) {
+				const uint32_t at_x = bs_ring_at<0>(e.x, wlb_at), at_0 = bs_ring_at<0>(e.y, wlb_at), at_1 = bs_ring_at<1>(e.y, wlb_at);
 				if constexpr (SGN) {
 					// no branch: an empty slot reads and writes the spare row.  (With a branch around the reads the compiler has
 					// to wait for the write of a pass before it may look at the next table entry.)
-					const int slot = (int) (e.x & 0xFFFFu);
-					const uint32_t x0 = ring[slot * RSTR + wlb];
-					const uint32_t v0 = ring[(e.y & 0xFFFFu) * RSTR + wlb];
-					const uint32_t v1 = ring[(e.y >> 16) * RSTR + wlb];          // (one dependency: the same row again, coefficient 0)
+					const uint32_t x0 = word(at_x), v0 = word(at_0), v1 = word(at_1);          // (one dependency: the same row again, coefficient 0)
+					int lo, hi;
+					sgn_unpack(x0, lo, hi);
+					sgn_mad_half<0, false>(v0, e.z, lo, hi);
+					sgn_mad_half<1, false>(v1, e.z, lo, hi);
+					word(at_x) = sgn_pack(sgn_reduce(lo, G), sgn_reduce(hi, G));
+				} else {
+					const uint32_t c0 = PLAIN ? (e.z & 0xFFFFu) : e.z, c1 = PLAIN ? (e.z >> 16) : e.w;
+					if (c0 != 0u) {          // (an empty slot has no coefficient)
+						uint32_t x = w_submul<PACKED, PLAIN>(word(at_x), word(at_0), c0, F, bm);
+						if (c1 != 0u)
+							x = w_submul<PACKED, PLAIN>(x, word(at_1), c1, F, bm);
+						word(at_x) = x;
+					}
+				}
+			};
+			// a row of a long pass: the first dependency inline, the others in the list; an empty slot has cnt = 0
+			auto long_row = [&](const uint4 e) {
+				const int rest = (int) (e.x >> 16) - 1;
+				const uint32_t at_x = bs_ring_at<0>(e.x, wlb_at);
+				if constexpr (SGN) {
+					const uint32_t x0 = word(at_x), v0 = word(bs_ring_at<0>(e.y, wlb_at));
 					int lo, hi;
 					sgn_unpack(x0, lo, hi);
 					sgn_mad(v0, (int) e.z, lo, hi);
-					sgn_mad(v1, (cnt > 2) ? 0 : (int) e.w, lo, hi);          // (more than two: .w is the offset of the others in the list)
-					if (__ballot(cnt > 2) != 0) {
-						if (cnt > 2) {
-							const int rest = cnt - 1;
-							for (int j = 0; j < rest; j += 4) {
-								uint2 em[4];
-								uint32_t wm[4];
+					for (int j = 0; j < rest; j += 4) {
+						uint2 em[4];
+						uint32_t wm[4];
 #pragma unroll
-								for (int t = 0; t < 4; t++)
-									em[t] = (j + t < rest) ? near[e.w + j + t] : uint2{(uint32_t) slot, 0u};
+						for (int t = 0; t < 4; t++)
+							em[t] = (j + t < rest) ? near[e.w + j + t] : uint2{e.x, 0u};
 #pragma unroll
-								for (int t = 0; t < 4; t++)
-									wm[t] = ring[em[t].x * RSTR + wlb];
-								lo = sgn_reduce(lo, G);          // (one term or four are in already: four more need a fresh start)
-								hi = sgn_reduce(hi, G);
+						for (int t = 0; t < 4; t++)
+							wm[t] = word(bs_ring_at<0>(em[t].x, wlb_at));
+						lo = sgn_reduce(lo, G);          // (one term or four are in already: four more need a fresh start)
+						hi = sgn_reduce(hi, G);
 #pragma unroll
-								for (int t = 0; t < 4; t++)
-									sgn_mad(wm[t], (int) em[t].y, lo, hi);
-							}
-						}
+						for (int t = 0; t < 4; t++)
+							sgn_mad(wm[t], (int) em[t].y, lo, hi);
 					}
-					ring[slot * RSTR + wlb] = sgn_pack(sgn_reduce(lo, G), sgn_reduce(hi, G));
-				} else if (cnt != 0) {
-					const int slot = (int) (e.x & 0xFFFFu);
-					uint32_t x = ring[slot * RSTR + wlb];
-					const uint32_t v0 = ring[(e.y & 0xFFFFu) * RSTR + wlb];
-					if (cnt <= 2) {
-						const uint32_t v1 = ring[(e.y >> 16) * RSTR + wlb];          // (one dependency: the same row again, coefficient 0)
-						if constexpr (SGN) {
-							int lo, hi;
-							sgn_unpack(x, lo, hi);
-							sgn_mad(v0, (int) e.z, lo, hi);
-							sgn_mad(v1, (int) e.w, lo, hi);
-							x = sgn_pack(sgn_reduce(lo, G), sgn_reduce(hi, G));
-						} else {
-							x = w_submul<PACKED, PLAIN>(x, v0, e.z, F, bm);
-							if (cnt == 2)
-								x = w_submul<PACKED, PLAIN>(x, v1, e.w, F, bm);
-						}
-					} else {
-						// the first dependency inline, the others in the list
-						const int rest = cnt - 1;
-						if constexpr (SGN) {
-							int lo, hi;
-							sgn_unpack(x, lo, hi);
-							sgn_mad(v0, (int) e.z, lo, hi);
-							for (int j = 0; j < rest; j += 4) {
-								uint2 em[4];
-								uint32_t wm[4];
-#pragma unroll
-								for (int t = 0; t < 4; t++)
-									em[t] = (j + t < rest) ? near[e.w + j + t] : uint2{(uint32_t) slot, 0u};
-#pragma unroll
-								for (int t = 0; t < 4; t++)
-									wm[t] = ring[em[t].x * RSTR + wlb];
-								lo = sgn_reduce(lo, G);          // (one term or four are in already: four more need a fresh start)
-								hi = sgn_reduce(hi, G);
-#pragma unroll
-								for (int t = 0; t < 4; t++)
-									sgn_mad(wm[t], (int) em[t].y, lo, hi);
-							}
-							x = sgn_pack(sgn_reduce(lo, G), sgn_reduce(hi, G));
-						} else {
-							x = w_submul<PACKED, PLAIN>(x, v0, e.z, F, bm);
-							for (int j = 0; j < rest; j++) {
-								const uint2 en = near[e.w + j];
-								x = w_submul<PACKED, PLAIN>(x, ring[en.x * RSTR + wlb], en.y, F, bm);
-							}
-						}
+					word(at_x) = sgn_pack(sgn_reduce(lo, G), sgn_reduce(hi, G));
+				} else if (rest >= 0) {
+					uint32_t x = w_submul<PACKED, PLAIN>(word(at_x), word(bs_ring_at<0>(e.y, wlb_at)), PLAIN ? (e.z & 0xFFFFu) : e.z, F, bm);
+					for (int j = 0; j < rest; j++) {
+						const uint2 en = near[e.w + j];
+						x = w_submul<PACKED, PLAIN>(x, word(bs_ring_at<0>(en.x, wlb_at)), en.y, F, bm);
 					}
-					ring[slot * RSTR + wlb] = x;
+					word(at_x) = x;
 				}
-				e = e_next;
+			};
+			// (the entry read ahead in the last trip is never used: it lies in the table, or in the first slots of the list behind it)
+			uint4 e = pe[0];
+			int it = 0, run = ch.nord * IPP;          // trips before the first long pass
+			while (it < niter) {
+				// (two trips per turn: the entry at hand and the one read ahead swap registers instead of being copied)
+				const int stop = min(it + run, niter);
+				for (; it + 1 < stop; it += 2) {
+					const uint4 e_odd = pe[(it + 1) * RSB];
+					ordinary(e);
+					e = pe[(it + 2) * RSB];
+					ordinary(e_odd);
+				}
+				if (it < stop) {
+					const uint4 e_next = pe[(it + 1) * RSB];
+					ordinary(e);
+					e = e_next;
+					it += 1;
+				}
+				if (it < niter) {
+					run = __builtin_amdgcn_readfirstlane((int) (e.y >> 16)) * IPP;          // ordinary trips up to the next long pass
+					for (int q = 0; q < IPP; q++, it++) {
+						const uint4 e_next = pe[(it + 1) * RSB];
+						long_row(e);
+						e = e_next;
+					}
+				}
 			}
 		}
 		lds_barrier();
@@ -1773,9 +1811,9 @@ template <bool PACKED, bool PLAIN, int LPR, int NW, bool SGN = false, int RING =
 void launch_backsolve_variant(const BsArgs &b, int Sm, hipStream_t stream, const BsImage &B)
 {
 	using G = BsGeom<PACKED, LPR, NW, RING, PASSROWS, PASSCAP>;
-	if (B.ring != RING || B.passrows != PASSROWS || B.passcap != PASSCAP)
-		die("backsolve: the plan was built for chunks of %d rows, passes of %d rows, %d passes; this kernel takes %d / %d / %d", B.ring, B.passrows,
-		    B.passcap, RING, PASSROWS, PASSCAP);
+	if (B.ring != RING || B.passrows != PASSROWS || B.passcap != PASSCAP || B.rstr != G::RSTR)
+		die("backsolve: the plan was built for chunks of %d rows, passes of %d rows, %d passes, ring rows %d words apart; this kernel takes %d / %d / %d / %d",
+		    B.ring, B.passrows, B.passcap, B.rstr, RING, PASSROWS, PASSCAP, G::RSTR);
 	static bool configured = false;
 	if (!configured) {
 		HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&backsolve_kernel<PACKED, PLAIN, LPR, NW, SGN, RING, PASSROWS, PASSCAP, WGS_PER_CU>),
@@ -1872,9 +1910,15 @@ void backsolve_plan(const FactPlan &P, spasm_hip_dfact *F, hipStream_t stream)
 		B.ring = (shape == 4) ? 1260 : (shape == 5) ? 1200 : BS_RING;
 		B.passrows = (shape >= 3) ? 64 : BS_PASSROWS;
 		B.passcap = (shape == 3) ? 31 : (shape == 4) ? 48 : (shape == 5) ? 44 : BS_PASSCAP;
+		// words of a slab row of that kernel (LPR in backsolve_build's table of shapes) + 1: BsGeom::RSTR
+		B.rstr = ((shape == 3) ? 8 : (shape == 4) ? 10 : (shape == 5) ? 12 : (shape == 2) ? 16 : 32) + 1;
 	}
 	const int PLAN_RING = B.ring, PLAN_PASSROWS = B.passrows, PLAN_PASSCAP = B.passcap;
-	const uint4 PLAN_EMPTY = uint4{(uint32_t) PLAN_RING, (uint32_t) PLAN_RING | ((uint32_t) PLAN_RING << 16), 0u, 0u};
+	// rows of the ring go into the tables as word offsets, slot * RSTR, in 16 bits (the spare row included)
+	const uint32_t PLAN_RSTR = (uint32_t) B.rstr;
+	if ((uint32_t) (PLAN_RING + 1) * PLAN_RSTR > 65535u)
+		die("backsolve_plan: a ring of %d + 1 rows, %u words apart: the offset of a row does not fit 16 bits", PLAN_RING, PLAN_RSTR);
+	const uint4 PLAN_EMPTY = bs_pass_empty((uint32_t) PLAN_RING * PLAN_RSTR);
 	// compact ids: labels that hold a row, in label (= level) order
 	std::vector<int> cid((size_t) (rpad > 0 ? rpad : 1), -1);
 	std::vector<int> label_of((size_t) (r > 0 ? r : 1), 0);
@@ -1989,6 +2033,7 @@ void backsolve_plan(const FactPlan &P, spasm_hip_dfact *F, hipStream_t stream)
 	// chunks, from the last row to the first
 	std::vector<BsChunk> chunks;
 	std::vector<int> chunk_extra;
+	std::vector<int> chunk_long;          // per chunk: passes of rows with more than two dependencies inside it
 	std::vector<uint4> ptab;
 	std::vector<uint2> near;
 	// rows of R go to the kernel as offsets, row * (words of a row / 256): see backsolve_kernel
@@ -2007,28 +2052,30 @@ void backsolve_plan(const FactPlan &P, spasm_hip_dfact *F, hipStream_t stream)
 	while (hi > 0) {
 		BsChunk ch{};
 		ch.hi = hi;
-		int lo = hi, nnear = 0, npass = 0, in_level = 0, last_level = -1;
+		int lo = hi, nnear = 0, npass = 0, in_level[2] = {0, 0}, last_level = -1;          // (in_level: ordinary rows, long rows)
 		while (lo > 0 && hi - lo < PLAN_RING) {
 			const int c = lo - 1;
 			int nc = 0;
 			for (uint64_t e = dep_rp[c]; e < dep_rp[c + 1]; e++)
 				nc += dep[e].x < (uint32_t) hi;
-			const bool new_pass = nc > 0 && (level[c] != last_level || in_level % PLAN_PASSROWS == 0);
+			// rows with more than two dependencies inside the chunk (long rows) have passes of their own, behind their level's others
+			const int kind = nc > 2 ? 1 : 0;
+			if (nc > 0 && level[c] != last_level)
+				in_level[0] = in_level[1] = 0;
+			const bool new_pass = nc > 0 && in_level[kind] % PLAN_PASSROWS == 0;
 			const int extra = nc > 2 ? nc - 1 : 0;
 			if (nnear + extra > BS_NEARCAP || nc > 65535 || (new_pass && npass + 1 > PLAN_PASSCAP))
 				break;                           // (the first row of a chunk never has dependencies inside it)
 			if (nc > 0) {
-				if (level[c] != last_level)
-					in_level = 0;
 				npass += new_pass ? 1 : 0;
-				in_level += 1;
+				in_level[kind] += 1;
 				last_level = level[c];
 				nnear += extra;
 			}
 			lo = c;
 		}
 		ch.lo = lo;
-		ch.npass = npass;
+		ch.npass = (unsigned short) npass;          // (<= PLAN_PASSCAP)
 		ch.nnear = nnear;
 		chunks.push_back(ch);
 		chunk_extra.push_back(0);
@@ -2046,70 +2093,99 @@ void backsolve_plan(const FactPlan &P, spasm_hip_dfact *F, hipStream_t stream)
 			total_near += ch.nnear;
 		}
 		ptab.assign((size_t) total_pass * (size_t) PLAN_PASSROWS, PLAN_EMPTY);
+		chunk_long.assign(chunks.size(), 0);
 		near.assign((size_t) total_near, uint2{0u, 0u});
 		auto fill_chunk = [&](size_t k) {
 			BsChunk &ch = chunks[k];
+			const size_t pt_end = (size_t) (ch.pass0 + ch.npass) * (size_t) PLAN_PASSROWS;
 			size_t pt = (size_t) ch.pass0 * (size_t) PLAN_PASSROWS;          // next slot of the table of passes
 			int nn = 0;                                                       // list entries of the chunk so far
-			int last_level = -1, extra = 0, in_level = 0;
-			for (int c = ch.hi - 1; c >= ch.lo; c--) {
-				int nc = 0, nf = 0;
-				uint2 first[2] = {uint2{BS_NONE, 0u}, uint2{BS_NONE, 0u}};
-				for (uint64_t e = dep_rp[c]; e < dep_rp[c + 1]; e++) {
-					if (dep[e].x < (uint32_t) ch.hi) {
-						nc += 1;
-					} else {
-						if (nf < 2) {
-							first[nf] = uint2{dep[e].x * ldw256, dep[e].y};
-						} else {
-							far_cnt[c] += 1;
-							extra = 1;
-						}
-						nf += 1;
-					}
-				}
-				if (nf > 0)
-					far_head[c] = make_head(first[0].x, first[0].y, first[1].x, first[1].y);
-				if (nc == 0)
-					continue;
-				if (level[c] != last_level || in_level % PLAN_PASSROWS == 0) {
-					// a new pass: the rest of the previous one stays empty
-					pt = (pt + (size_t) PLAN_PASSROWS - 1) / (size_t) PLAN_PASSROWS * (size_t) PLAN_PASSROWS;
-					if (level[c] != last_level)
-						in_level = 0;
-					last_level = level[c];
-				}
-				in_level += 1;
-				uint4 en{(uint32_t) (c - ch.lo) | ((uint32_t) nc << 16), 0u, 0u, 0u};
+			int extra = 0;
+			std::vector<int> rows[2];          // rows of the level at hand with dependencies inside the chunk: ordinary, long
+			std::vector<int> long_at;          // the passes of long rows, counted from the chunk's first pass
+			auto off = [&](uint32_t row) -> uint32_t { return (row - (uint32_t) ch.lo) * PLAN_RSTR; };          // offset in the ring
+			auto put = [&](int c, bool is_long) {
+				int nc = 0;
+				for (uint64_t e = dep_rp[c]; e < dep_rp[c + 1]; e++)
+					nc += dep[e].x < (uint32_t) ch.hi;
+				uint4 en{off((uint32_t) c) | (is_long ? (uint32_t) nc << 16 : 0u), 0u, 0u, 0u};
 				int seen = 0;
 				for (uint64_t e = dep_rp[c]; e < dep_rp[c + 1]; e++) {
 					if (dep[e].x >= (uint32_t) ch.hi)
 						continue;
-					const uint32_t slot = dep[e].x - (uint32_t) ch.lo;
+					const uint32_t at = off(dep[e].x);
 					if (seen == 0) {
-						en.y = slot | (slot << 16);          // (one dependency: the second slot repeats it with coefficient 0)
-						en.z = dep[e].y;
-						if (nc > 2)
+						en.y = is_long ? at : at | (at << 16);          // (one dependency: the second slot repeats it with coefficient 0)
+						en.z = B.plain ? (dep[e].y & 0xFFFFu) : dep[e].y;
+						if (is_long)
 							en.w = (uint32_t) nn;
-					} else if (nc == 2) {
-						en.y = (en.y & 0xFFFFu) | (slot << 16);
-						en.w = dep[e].y;
+					} else if (!is_long) {
+						en.y = (en.y & 0xFFFFu) | (at << 16);
+						if (B.plain)
+							en.z |= dep[e].y << 16;
+						else
+							en.w = dep[e].y;
 					} else {
 						if (nn >= ch.nnear)
 							die("backsolve_plan: chunk %zu holds more list entries than the %d counted", k, ch.nnear);
-						near[(size_t) ch.near0 + (size_t) nn] = uint2{slot, dep[e].y};
+						near[(size_t) ch.near0 + (size_t) nn] = uint2{at, dep[e].y};
 						nn += 1;
 					}
 					seen += 1;
 				}
-				if (pt >= (size_t) (ch.pass0 + ch.npass) * (size_t) PLAN_PASSROWS)
-					die("backsolve_plan: chunk %zu needs more than the %d passes counted", k, ch.npass);
+				if (pt >= pt_end)
+					die("backsolve_plan: chunk %zu needs more than the %d passes counted", k, (int) ch.npass);
 				ptab[pt++] = en;
+			};
+			for (int c = ch.hi - 1; c >= ch.lo;) {
+				const int lvl = level[c];
+				rows[0].clear();
+				rows[1].clear();
+				for (; c >= ch.lo && level[c] == lvl; c--) {
+					int nc = 0, nf = 0;
+					uint2 first[2] = {uint2{BS_NONE, 0u}, uint2{BS_NONE, 0u}};
+					for (uint64_t e = dep_rp[c]; e < dep_rp[c + 1]; e++) {
+						if (dep[e].x < (uint32_t) ch.hi) {
+							nc += 1;
+						} else {
+							if (nf < 2) {
+								first[nf] = uint2{dep[e].x * ldw256, dep[e].y};
+							} else {
+								far_cnt[c] += 1;
+								extra = 1;
+							}
+							nf += 1;
+						}
+					}
+					if (nf > 0)
+						far_head[c] = make_head(first[0].x, first[0].y, first[1].x, first[1].y);
+					if (nc > 0)
+						rows[nc > 2 ? 1 : 0].push_back(c);
+				}
+				// the ordinary rows of the level, then its long rows: each kind starts a pass, the rest of the one before stays empty
+				for (int kind = 0; kind < 2; kind++)
+					for (size_t q = 0; q < rows[kind].size(); q++) {
+						if (q % (size_t) PLAN_PASSROWS == 0) {
+							pt = (pt + (size_t) PLAN_PASSROWS - 1) / (size_t) PLAN_PASSROWS * (size_t) PLAN_PASSROWS;
+							if (kind == 1)
+								long_at.push_back((int) (pt / (size_t) PLAN_PASSROWS) - ch.pass0);
+						}
+						put(rows[kind][q], kind == 1);
+					}
 			}
 			const int passes = (int) ((pt + (size_t) PLAN_PASSROWS - 1) / (size_t) PLAN_PASSROWS) - ch.pass0;
 			if (passes != ch.npass || nn != ch.nnear)
-				die("backsolve_plan: chunk %zu was counted differently on the second pass (%d passes against %d, %d list entries against %d)", k, passes, ch.npass, nn,
-				    ch.nnear);
+				die("backsolve_plan: chunk %zu was counted differently on the second pass (%d passes against %d, %d list entries against %d)", k, passes,
+				    (int) ch.npass, nn, ch.nnear);
+			// where the long passes are: the descriptor leads to the first, every slot of a long pass (.y, high half) to the next
+			ch.nord = long_at.empty() ? ch.npass : (unsigned short) long_at[0];
+			for (size_t q = 0; q < long_at.size(); q++) {
+				const uint32_t ordinary_after = (uint32_t) ((q + 1 < long_at.size() ? long_at[q + 1] : (int) ch.npass) - long_at[q] - 1);
+				uint4 *pass = &ptab[(size_t) (ch.pass0 + long_at[q]) * (size_t) PLAN_PASSROWS];
+				for (int t = 0; t < PLAN_PASSROWS; t++)
+					pass[t].y = (pass[t].y & 0xFFFFu) | (ordinary_after << 16);
+			}
+			chunk_long[k] = (int) long_at.size();
 			chunk_extra[k] = extra;
 			// everything the kernel needs to start a chunk sits in its descriptor (no dependent loads at the top of a chunk)
 			ch.np0 = (int) std::min<uint64_t>(np_rp[ch.lo], 0x7FFFFFFFull);
@@ -2146,14 +2222,17 @@ void backsolve_plan(const FactPlan &P, spasm_hip_dfact *F, hipStream_t stream)
 	lap("chunks, passes, near and far tables");
 	if (verbose() >= 3) {
 		// how full the passes of phase B are (an empty slot costs a lane what a row does), and why: the widths of the levels
-		int64_t passes = 0, used = 0;
+		int64_t passes = 0, used = 0, long_passes = 0;
 		for (const BsChunk &ch : chunks)
 			passes += ch.npass;
+		for (const int n : chunk_long)
+			long_passes += n;
 		for (const uint4 &en : ptab)
-			used += (en.x >> 16) != 0;
-		logmsg("[factor image/back-substitution plan] shape %d: %zu chunks of <= %d rows, %lld passes of %d slots, %lld of %lld slots occupied (%.1f%%), "
-		       "%d rows in %d levels\n", B.shape, chunks.size(), PLAN_RING, (long long) passes, PLAN_PASSROWS, (long long) used,
-		       (long long) passes * PLAN_PASSROWS, passes > 0 ? 100.0 * (double) used / (double) (passes * PLAN_PASSROWS) : 0.0, r, P.nlevels);
+			used += en.z != 0u;          // (a row in the table has a first coefficient; entries of U are not 0)
+		logmsg("[factor image/back-substitution plan] shape %d: %zu chunks of <= %d rows, %lld passes of %d slots, %lld of them of long rows (more than two "
+		       "dependencies inside the chunk), %lld of %lld slots occupied (%.1f%%), %d rows in %d levels\n", B.shape, chunks.size(), PLAN_RING,
+		       (long long) passes, PLAN_PASSROWS, (long long) long_passes, (long long) used, (long long) passes * PLAN_PASSROWS,
+		       passes > 0 ? 100.0 * (double) used / (double) (passes * PLAN_PASSROWS) : 0.0, r, P.nlevels);
 		int64_t hist_levels[32] = {0}, hist_rows[32] = {0};          // bucket b: widths in (2^(b-1), 2^b]
 		for (int l = 0; l < P.nlevels; l++) {
 			const int w = P.lvl_count[l];

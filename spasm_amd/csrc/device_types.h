@@ -131,7 +131,9 @@ struct FactPlan {
 // Rows are numbered by COMPACT id = rank of their label among the labels that hold a row (so level order).
 struct BsChunk {              // a run of consecutive compact rows solved inside LDS by one workgroup per column slab
 	int lo, hi;               // compact rows [lo, hi)
-	int pass0, npass;         // phase-B passes of 32 rows (rows of one level that have dependencies inside the chunk)
+	int pass0;                // phase-B passes (rows of one level that have dependencies inside the chunk): the first one, ...
+	unsigned short npass;     // ... their number, ...
+	unsigned short nord;      // ... and how many ordinary passes come before the first pass of long rows (npass: there is none)
 	int near0, nnear;         // dependencies of the rows that have more than two of them inside the chunk
 	int np0;                  // first non-pivotal entry (index into d_np) of the rows of the chunk ...
 	int npn;                  // ... their number (bits 0-30); bit 31: some row has more than two dependencies outside the chunk
@@ -149,9 +151,9 @@ struct BsImage {
 	bool sgn = false;                 // ... negated balanced residues, and R holds signed 16-bit entries (small p: backsolve.hip, SgnDev)
 	int *d_col = nullptr;             // column -> compact row id of its pivot, or r + index among the non-pivotal columns
 	BsChunk *d_chunk = nullptr;
-	uint4 *d_ptab = nullptr;          // 32 entries per pass: (slot | count << 16, dep0 | dep1 << 16, coefficient 0, coefficient 1); a row
+	uint4 *d_ptab = nullptr;          // `passrows` entries per pass, ring rows as word offsets slot * rstr (layout: bs_pass_empty in backsolve.hip); a row
 	                                  // with more than two dependencies keeps the first inline, (offset into d_near - near0) in .w, the others there
-	uint2 *d_near = nullptr;          // (slot of the dependency, coefficient)
+	uint2 *d_near = nullptr;          // (word offset of the dependency's row in the ring, coefficient)
 	uint4 *d_far_head = nullptr;      // per compact row: its first two dependencies outside the chunk, rows as offsets (bs_head in backsolve.hip); ~0: none
 	uint64_t *d_far_rp = nullptr;     // per compact row: the others, [r + 1] offsets into d_far
 	uint2 *d_far = nullptr;
@@ -166,6 +168,7 @@ struct BsImage {
 	char kernel_build[64] = "backsolve_kernel";      // variant launched by the last build, as rocprofv3 prints it
 	int shape = 2;                    // workgroup shape of the build kernel the plan was cut for (backsolve_plan)
 	int ring = 768, passrows = 32, passcap = 80;      // rows per chunk, rows per phase-B pass, passes per chunk of that plan
+	int rstr = 17;                    // words between two rows of that kernel's LDS ring: the unit of the row offsets in d_ptab and d_near
 };
 
 // ---- sparse back-substituted factor ("sparse image", sparse_image.hip) ----------------------------
