@@ -1494,6 +1494,180 @@ __global__ __launch_bounds__(512) void bs_apply_s16_csr_kernel(ApplyArgs d)
 	}
 }
 
+// The same with ONE row buffer per wave: the older pending row (length published, offset not known yet) waits in a static
+// register file, one packed word per lane and tile, instead of a second LDS buffer -- half the LDS per wave, so twice the waves
+// on a CU (mk13.b5: 12 KB against 22 KB).  NT = 64-word tiles of a row (Smpad = 128 NT columns, a multiple of AP_TU).  The
+// state machine is the one above with "x0" = the register file and "x1" = the LDS buffer: a row is always computed in LDS; at
+// the next turn it is handed over to the registers (NT ds_reads at static indices), after the row that waited there has been
+// settled -- with `wait` exactly where the kernel above waits with both buffers taken.  Every index into the register file is
+// a compile-time constant (the emit loop is unrolled over the tile groups): a dynamic one would turn the file into scratch.
+// DEEP: as s16_reduce_segment.  WPE: waves per SIMD the register allocation must leave room for.
+constexpr int CSR_ROWREG_MAX_TILES = 40;            // widest instantiation: Smpad = 5,120 columns, 40 registers
+constexpr bool CSR_ROWREG_DEEP = false;
+constexpr int CSR_ROWREG_WPE = 4;
+
+template <int NT, bool DEEP, int WPE>
+__global__ __launch_bounds__(512, WPE) void bs_apply_s16_csr_rowreg_kernel(ApplyArgs d)
+{
+	static_assert(NT % AP_TU == 0 && NT >= AP_TU && NT <= CSR_ROWREG_MAX_TILES, "whole tile groups");
+	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+	const SchurArgs &a = d.a;
+	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+	const MontDev F = a.F;
+	const SgnDev G = d.G;
+	constexpr int nwords = 64 * NT;                      // the whole row: one segment
+	constexpr int NG = NT / AP_TU;                       // tile groups of a row
+	constexpr int GW = 64 * AP_TU;                       // words of a group
+	unsigned char *area = lds_raw + (size_t) wave * d.wave_bytes;
+	uint2 *plist = reinterpret_cast<uint2 *>(area);
+	int *cbuf = reinterpret_cast<int *>(area);           // (the list is not in use while a row is written)
+	uint32_t *xl = reinterpret_cast<uint32_t *>(area + CSR_SCRATCH_BYTES);
+	unsigned long long st_input = 0, st_piv = 0;
+	int st_done = 0;
+	bool lost = false;
+	// rows whose offset was not known yet (-1: none; wave-uniform): k0 in the register file (the older one), k1 in the LDS buffer
+	RegFile<uint32_t, NT> xr;
+	int k0 = -1, c0 = 0, k1 = -1, c1 = 0;
+
+	// row k0 to Sj / Sx once its offset is known (one look, or looks until it is with `wait`); false: not known yet
+	auto settle = [&](bool wait) -> bool {
+		unsigned long long end = 0;
+		if (!lookback_probe(d, k0, lane, wait, end, lost))
+			return false;
+		const int64_t off = (int64_t) (end - (unsigned long long) c0);
+		const bool fits = !lost && end <= (unsigned long long) d.cap;
+		if (lane == 0) {
+			d.Sp[k0] = off;
+			if (k0 == a.nrows - 1)
+				d.Sp[a.nrows] = (int64_t) end;
+			if (!fits)
+				atomicOr(&a.ctr[CTR_STATUS], 1);
+		}
+		if (fits && c0 > 0) {
+			// as in the kernel above, the words from the register file: the group index is a compile-time constant
+			int *oj = d.Sj + off, *ox = d.Sx + off;
+			uint32_t wpos = 0;
+			int2 qa[AP_TU], qb[AP_TU], qc[AP_TU];
+			// (the byte offset of a group goes through an empty asm: as constants, the 64-bit addresses of every group would be
+			//  formed once before the loop over the rows and held in two registers each)
+			auto issue = [&](int t0, int2 (&qq)[AP_TU]) {
+				uint32_t at = (uint32_t) (t0 + lane) * (uint32_t) sizeof(int2);
+				asm volatile("" : "+v"(at));
+				const int2 *qg = reinterpret_cast<const int2 *>(reinterpret_cast<const char *>(a.q) + at);
+#pragma unroll
+				for (int u = 0; u < AP_TU; u++)
+					qq[u] = qg[64 * u];
+			};
+			// lane l of a tile holds columns 2 (t0 + l) and 2 (t0 + l) + 1: entries come out sorted by column
+			auto emit = [&](auto gg, const int2 (&qq)[AP_TU]) {
+				constexpr int g = decltype(gg)::value;
+				int v0[AP_TU], v1[AP_TU];
+				uint32_t dst[AP_TU], gpos = 0;
+				bs_static_for<0, AP_TU>([&](auto uu) {
+					constexpr int u = decltype(uu)::value;
+					sgn_unpack(xr.template at<g * AP_TU + u>(), v0[u], v1[u]);
+					v0[u] = sgn_canonical(v0[u], G);
+					v1[u] = sgn_canonical(v1[u], G);
+					const uint64_t m0 = __ballot(v0[u] != 0), m1 = __ballot(v1[u] != 0);
+					uint32_t at = gpos;
+					at = __builtin_amdgcn_mbcnt_hi((uint32_t) (m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m0, at));
+					at = __builtin_amdgcn_mbcnt_hi((uint32_t) (m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m1, at));
+					dst[u] = at;
+					if (v0[u] != 0)
+						cbuf[at] = qq[u].x;
+					if (v1[u] != 0)
+						cbuf[at + (v0[u] != 0 ? 1u : 0u)] = qq[u].y;
+					gpos += (uint32_t) (__popcll(m0) + __popcll(m1));
+				});
+				for (uint32_t t = lane; t < gpos; t += 64)
+					oj[wpos + t] = cbuf[t];
+#pragma unroll
+				for (int u = 0; u < AP_TU; u++) {
+					if (v0[u] != 0)
+						cbuf[dst[u]] = v0[u];
+					if (v1[u] != 0)
+						cbuf[dst[u] + (v0[u] != 0 ? 1u : 0u)] = v1[u];
+				}
+				for (uint32_t t = lane; t < gpos; t += 64)
+					ox[wpos + t] = cbuf[t];
+				wpos += gpos;
+			};
+			// the columns of the next two groups are in flight during the stores of a group
+			issue(0, qa);
+			if constexpr (NG > 1)
+				issue(GW, qb);
+			bs_static_for<0, NG>([&](auto gg) {
+				constexpr int g = decltype(gg)::value;
+				if constexpr (g % 3 == 0) {
+					if constexpr (g + 2 < NG)
+						issue((g + 2) * GW, qc);
+					emit(gg, qa);
+				} else if constexpr (g % 3 == 1) {
+					if constexpr (g + 2 < NG)
+						issue((g + 2) * GW, qa);
+					emit(gg, qb);
+				} else {
+					if constexpr (g + 2 < NG)
+						issue((g + 2) * GW, qb);
+					emit(gg, qc);
+				}
+			});
+		}
+		st_done += fits ? 1 : 0;
+		k0 = -1;
+		return true;
+	};
+	// the row in the LDS buffer becomes the older pending row (the register file is free)
+	auto hand_over = [&]() {
+		bs_static_for<0, NT>([&](auto tt) {
+			constexpr int t = decltype(tt)::value;
+			xr.template at<t>() = xl[64 * t + lane];
+		});
+		k0 = k1;
+		c0 = c1;
+		k1 = -1;
+	};
+
+	// at the top of a turn: nothing pending, or k1 alone (the row of the last turn), or both
+	for (bool finishing = false;;) {
+		if (k1 >= 0 && k0 < 0)
+			hand_over();
+		if (k0 >= 0)
+			settle(k1 >= 0 || finishing);          // one look; with both taken (and at the end), until the older row is written
+		if (k1 >= 0)
+			hand_over();
+		if (finishing)
+			break;
+		const int k = next_ticket(d, lane);
+		if (k >= a.nrows) {
+			finishing = true;
+			continue;
+		}
+		const int i = a.rows[k];
+		const int64_t lo = a.Ap[i], hi = a.Ap[i + 1];
+		st_input += (unsigned long long) (hi - lo);
+		int count = s16_reduce_segment<DEEP>(d, F, G, lo, hi, 0, nwords, plist, xl, lane, true, st_piv);
+		if (count < 0) {                     // no pivotal entry in the last batch: the row was not swept
+			count = 0;
+			for (int t0 = 0; t0 < nwords; t0 += 64) {
+				const uint32_t w = xl[t0 + lane];
+				count += __popcll(__ballot((w & 0xFFFFu) != 0)) + __popcll(__ballot((w >> 16) != 0));
+			}
+		}
+		if (lane == 0)
+			__hip_atomic_store(&d.status[k], LB_FLAG_LEN | (unsigned long long) count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		k1 = k;
+		c1 = count;
+	}
+	if (lane == 0) {
+		if (lost)
+			atomicOr(&a.ctr[CTR_STATUS], 4);
+		atomicAdd(&a.ctr64[C64_INPUT], st_input);
+		atomicAdd(&a.ctr64[C64_ELIM], st_piv);
+		atomicAdd(&a.ctr[a.done_ctr], st_done);
+	}
+}
+
 // ---- staged sparse output (signed 16-bit entries) --------------------------------------------------
 // Writing the rows of S in order from ONE kernel makes every row wait for the lengths of the rows before it -- with
 // 3584 rows in flight a row waits for the slowest of its several hundred running predecessors, a third of its own time
@@ -2447,15 +2621,39 @@ bool backsolve_stages_output(const spasm_hip_dfact *F, int64_t *row_bytes)
 	return B.planned && env_int("SPASM_HIP_BS_STAGED", 1) != 0;
 }
 
-// bytes of LDS a wave of bs_apply_s16_csr_kernel needs: the list / compaction area and two row buffers
-static size_t csr_wave_bytes(int64_t ldR)
+// bytes of LDS a wave of the CSR-output kernels needs: the list / compaction area and its row buffers (two, or one beside the
+// register file of bs_apply_s16_csr_rowreg_kernel)
+static size_t csr_wave_bytes(int64_t ldR, int buffers)
 {
-	return (size_t) CSR_SCRATCH_BYTES + 2 * (size_t) ldR * 2;
+	return (size_t) CSR_SCRATCH_BYTES + (size_t) buffers * (size_t) ldR * 2;
 }
 
-// The staged output of a batch replaced by bs_apply_s16_csr_kernel (rows of S straight to Sj / Sx)?  Signed 16-bit entries,
-// rows of one segment (<= 24,576 columns), the whole batch in one slice of the staging buffer, two rows per wave within what a
-// workgroup may have.  SPASM_HIP_BS_CSR=0 keeps the staged kernels (A/B runs, tests).
+// 64-word tiles of a row when bs_apply_s16_csr_rowreg_kernel takes the batch; 0: rows wider than its widest instantiation, or
+// SPASM_HIP_BS_CSR_ROWREG=0 (A/B runs, tests): the two-buffer kernel
+static int csr_rowreg_tiles(int64_t ldR)
+{
+	if (ldR > 128 * CSR_ROWREG_MAX_TILES || env_int("SPASM_HIP_BS_CSR_ROWREG", 1) == 0)
+		return 0;
+	return (int) (ldR / 128);
+}
+
+using CsrKernel = void (*)(ApplyArgs);
+static CsrKernel csr_kernel(int tiles)
+{
+	switch (tiles) {
+	case 0: return bs_apply_s16_csr_kernel;
+#define ROWREG_CASE(NT) case NT: return bs_apply_s16_csr_rowreg_kernel<NT, CSR_ROWREG_DEEP, CSR_ROWREG_WPE>;
+	ROWREG_CASE(4) ROWREG_CASE(8) ROWREG_CASE(12) ROWREG_CASE(16) ROWREG_CASE(20)
+	ROWREG_CASE(24) ROWREG_CASE(28) ROWREG_CASE(32) ROWREG_CASE(36) ROWREG_CASE(40)
+#undef ROWREG_CASE
+	}
+	die("launch_backsolve_apply: no CSR-output kernel for rows of %d tiles", tiles);
+	return nullptr;
+}
+
+// The staged output of a batch replaced by the CSR-output kernels (rows of S straight to Sj / Sx)?  Signed 16-bit entries,
+// rows of one segment (<= 24,576 columns), the whole batch in one slice of the staging buffer, the row buffers of a wave within
+// what a workgroup may have.  SPASM_HIP_BS_CSR=0 keeps the staged kernels (A/B runs, tests).
 bool backsolve_output_csr(const spasm_hip_dfact *F, int64_t nrows, int64_t stage_rows)
 {
 	const BsImage &B = F->bs;
@@ -2464,7 +2662,7 @@ bool backsolve_output_csr(const spasm_hip_dfact *F, int64_t nrows, int64_t stage
 	int dev = 0, per_block = 0;
 	HIP_CHECK(hipGetDevice(&dev));
 	HIP_CHECK(hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-	return csr_wave_bytes(B.ldR) <= (size_t) per_block;
+	return csr_wave_bytes(B.ldR, csr_rowreg_tiles(B.ldR) > 0 ? 1 : 2) <= (size_t) per_block;
 }
 
 // S rows from R: sparse rows into the pool of `a` (dense_out == nullptr) or dense rows.
@@ -2515,16 +2713,27 @@ void launch_backsolve_apply(const SchurArgs &a, const spasm_hip_dfact *F, uint32
 		return;
 	}
 	if (direct != nullptr && direct->csr && dense_out == nullptr) {
-		// rows of S from their LDS buffers straight to Sj / Sx.  Workgroup shape: the one that puts the most waves on a CU
-		// (160 KB of LDS), the larger workgroup on a tie
-		const size_t per_wave = csr_wave_bytes(B.ldR);
+		// rows of S straight to Sj / Sx: the older pending row of a wave in registers (rows of up to 5,120 columns), or both in LDS
+		const int tiles = csr_rowreg_tiles(B.ldR);
+		const CsrKernel kernel = csr_kernel(tiles);
+		const size_t per_wave = csr_wave_bytes(B.ldR, tiles > 0 ? 1 : 2);
 		int per_block = 0;
 		HIP_CHECK(hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-		int waves = 1, best = 0;
-		for (int w = 1; w <= 8 && (size_t) w * per_wave <= (size_t) per_block; w++) {
-			const int fit = (int) ((size_t) (160 * 1024) / ((size_t) w * per_wave)) * w;
-			if (fit >= best) {
-				best = fit;
+		const int max_waves = (int) std::min<size_t>(8, (size_t) per_block / per_wave);
+		// (set at every launch: the attribute belongs to the device the call runs on, and a process may drive several)
+		HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+		                              (int) (per_wave * (size_t) max_waves)));
+		// Workgroup shape: the one that puts the most waves on a CU, the larger workgroup on a tie.  What a CU holds is asked of
+		// the kernel that is launched, with its LDS (160 KB per CU) and its registers.  A row's offset waits for the lengths of
+		// rows that other workgroups hold: every workgroup of the grid must be resident, so this figure also bounds the grid.
+		int waves = 1, per_cu = 0;
+		for (int w = 1; w <= max_waves; w++) {
+			const size_t lds_w = per_wave * (size_t) w;
+			int fit = 0;
+			HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, kernel, 64 * w, lds_w));
+			fit = std::min(fit, (int) ((size_t) (160 * 1024) / lds_w));
+			if (fit * w >= per_cu * waves) {
+				per_cu = fit;
 				waves = w;
 			}
 		}
@@ -2532,22 +2741,15 @@ void launch_backsolve_apply(const SchurArgs &a, const spasm_hip_dfact *F, uint32
 		d.wave_bytes = per_wave;
 		d.seg_words = d.Smpad / 2;
 		const size_t lds = per_wave * (size_t) waves;
-		static size_t configured = 0;
-		if (lds > configured) {
-			HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&bs_apply_s16_csr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-			configured = lds;
-		}
-		// a row's offset waits for the lengths of rows that other workgroups hold: every workgroup of the grid resident
-		int per_cu = 0;
-		HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, bs_apply_s16_csr_kernel, 64 * waves, lds));
-		per_cu = std::min(per_cu, (int) ((size_t) (160 * 1024) / lds));
 		if (per_cu < 1)
 			die("launch_backsolve_apply: %zu bytes of LDS per workgroup leave no room for the CSR output", lds);
 		const int blocks = std::max(1, std::min((a.nrows + waves - 1) / waves, prop.multiProcessorCount * per_cu));
 		d.ntickets = std::min(LB_TICKETS, blocks);
+		direct->csr_tiles = tiles;
 		if (verbose() >= 3)
-			logmsg("[dense image] CSR output: %d workgroups of %d waves, %zu bytes of LDS each, %d per CU\n", blocks, waves, lds, per_cu);
-		hipLaunchKernelGGL(bs_apply_s16_csr_kernel, dim3(blocks), dim3(64 * waves), lds, stream, d);
+			logmsg("[dense image] CSR output (%s): %d workgroups of %d waves, %zu bytes of LDS each, %d per CU\n",
+			       tiles > 0 ? "pending row in registers" : "two row buffers", blocks, waves, lds, per_cu);
+		hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64 * waves), lds, stream, d);
 		HIP_CHECK(hipGetLastError());
 		return;
 	}

@@ -1949,6 +1949,7 @@ int dschur_impl(const spasm_hip_dcsr *A, const int *d_rows, int nrows, const spa
 
 	bool used_bs = false, built_bs = false, bs_direct = false, use_pull = false;
 	int bs_staged_slices = 0;          // staged output of the back-substituted path: slices it ran in (0: not used)
+	int bs_csr_tiles = -1;             // CSR output of the back-substituted path: BsDirectOut::csr_tiles of the launch
 	if (want_sp) {
 		group_mode = 0;
 		HIP_CHECK(hipEventRecord(W->ev[5], stream));
@@ -2017,6 +2018,7 @@ int dschur_impl(const spasm_hip_dcsr *A, const int *d_rows, int nrows, const spa
 			}
 			launch_backsolve_apply(a, F, nullptr, 0, stream, &out);
 			bs_staged_slices = out.staged ? out.slices : 0;
+			bs_csr_tiles = out.csr_tiles;
 		} else {
 			launch_backsolve_apply(a, F, nullptr, 0, stream, nullptr);
 		}
@@ -2245,7 +2247,9 @@ eliminated:
 				}
 			}
 			char apply_name[32];
-			if (B.sgn)
+			if (B.sgn && bs_csr_tiles == 0)          // (the CSR output's two-buffer kernel: wide rows, A/B runs)
+				snprintf(apply_name, sizeof(apply_name), "bs_apply_s16_kernel<lds2>");
+			else if (B.sgn)
 				snprintf(apply_name, sizeof(apply_name), "bs_apply_s16_kernel");
 			else
 				snprintf(apply_name, sizeof(apply_name), "bs_apply_kernel<%s,%s>", B.elem_bytes == 2 ? "true" : "false", B.plain ? "true" : "false");
