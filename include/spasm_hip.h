@@ -49,9 +49,10 @@
  *   SPASM_HIP_BS_CSR=0|1          dense image, signed 16-bit entries: rows of S through the staged output (packed rows, scan, expansion) /
  *                                 straight to their CSR place from the apply kernel (default 1 wherever a row is one segment and the
  *                                 batch one slice) -- A/B runs and the tests' way to compare the two
- *   SPASM_HIP_BS_CSR_ROWREG=0|1   ... the CSR output with two LDS row buffers per wave / with one, the older pending row of a wave held
- *                                 in registers (default 1 for rows of up to 5,120 non-pivotal columns; wider rows always take two
- *                                 buffers).  The statistics name the two-buffer kernel bs_apply_s16_kernel<lds2>
+ *   SPASM_HIP_BS_CSR_ROWREG=0|1   ... the CSR output (bs_apply_s16_csr_kernel) with two LDS row buffers per wave (its PendingLds policy) /
+ *                                 with one, the older pending row of a wave held in registers (PendingRegs; default 1 for rows of up to
+ *                                 5,120 non-pivotal columns; wider rows always take two buffers).  The statistics name the two-buffer
+ *                                 instantiation bs_apply_s16_kernel<lds2>
  *   SPASM_HIP_KERNEL_POOL=n       spasm_hip_kernel_basis: entries of the first pool handed to spasm_hip_dschur (default: the rule of
  *                                 spasm_hip_schur) -- the tests' way to the retry with a larger pool
  */
@@ -456,8 +457,8 @@ typedef struct {
 	int backsolve_built;    /* 1: ... and R was (re)built by this call (ms_backsolve, bytes_backsolve say at what cost) */
 	float ms_backsolve;     /* device time of building R = U_pp^-1 U_pn (memset + init + backsolve_kernel) */
 	float ms_apply;         /* device time of the apply kernel (S rows from R): bs_apply_kernel, or bs_apply_s16_kernel (the name
-	                           `kernel` / `kernel_other` give for bs_apply_s16_csr_rowreg_kernel too, which writes S itself;
-	                           bs_apply_s16_kernel<lds2> is bs_apply_s16_csr_kernel, its form with two LDS row buffers) */
+	                           `kernel` / `kernel_other` give for bs_apply_s16_csr_kernel too, which writes S itself;
+	                           bs_apply_s16_kernel<lds2> is its PendingLds instantiation, with two LDS row buffers) */
 	i64 bytes_backsolve;    /* algorithmic bytes of that build */
 	i64 bytes_apply;        /* ... of the apply kernel */
 	char kernel[64];        /* name of the dominant elimination kernel this call launched, as rocprofv3 shows it (the apply kernels

@@ -716,9 +716,9 @@ struct ApplyArgs {
 	int *Sj;
 	int *Sx;
 	int64_t cap;
-	int dbg;                      // always 0 (bit 3 = no loads of R, 4 = no look-back, 5 = no output stores: timing experiments, wrong
-	                              // results).  Kept: bs_apply_s16_kernel measured ~3 % slower without the branches on it (close to its
-	                              // run-to-run spread; not settled)
+	int dbg;                      // always 0 (bit 3 = no loads of R, 5 = no output stores: timing experiments, wrong results).  Kept:
+	                              // bs_apply_s16_kernel measured ~3 % slower without the branches on it (close to its run-to-run
+	                              // spread; not settled)
 	int sgn;                      // R holds signed 16-bit entries (SgnDev)
 	SgnDev G;
 	unsigned long long *block_sum; // staged output: sum of the lengths of every block of SCAN_BLOCK rows (zeroed before the launch)
@@ -727,8 +727,6 @@ struct ApplyArgs {
 };
 
 constexpr unsigned long long LB_FLAG_LEN = 1ull << 62, LB_FLAG_END = 2ull << 62, LB_VALUE = (1ull << 62) - 1;
-constexpr int LB_PER_LANE = 1;             // predecessors inspected per lane and poll (64 per wave: 8 -> 4.23, 4 -> 3.93, 2 -> 3.69, 1 -> 3.50 ms)
-
 
 // Rows are handed out in (nearly) increasing order, each to a wave that starts it at once: whoever waits for a row in the
 // look-back below knows a running wave holds it.  One counter would serve every wave of the chip -- returning atomics on
@@ -750,40 +748,32 @@ __device__ __forceinline__ int next_ticket(const ApplyArgs &d, int lane)
 
 // Ordered output without a second pass (single-pass chained scan): row k publishes its length, adds up the lengths of
 // the rows before it, back to the nearest row that already knows where it ends, and publishes its own end.  Rows are
-// handed out by next_ticket().  Returns the offset of row k.
-__device__ __forceinline__ unsigned long long lookback_offset(const ApplyArgs &d, int k, int count, int lane, bool &lost)
+// handed out by next_ticket().
+__device__ __forceinline__ void lb_publish_length(const ApplyArgs &d, int k, int count, int lane)
 {
 	if (lane == 0)
 		__hip_atomic_store(&d.status[k], LB_FLAG_LEN | (unsigned long long) count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-	unsigned long long prior = 0;
+}
+
+// One look back from row k (its length published): the status words of row k and the 63 rows before it, then further back
+// while no end is found.  true: end = offset past row k.  false: a row in between has not published its length yet -- only
+// without `wait`; with it the look is repeated (after 2^24 polls `lost` is set and true returned).  A look that succeeds also
+// publishes the ends of the rows of its first window that had only their lengths (row k among them), so that the next look
+// stops close by.
+__device__ __forceinline__ bool lookback_probe(const ApplyArgs &d, int k, int lane, bool wait, unsigned long long &end, bool &lost)
+{
+	unsigned long long total = 0, near = 0;          // near: length of this lane's row in the first window (rows before its nearest end)
+	int near_end = -1;                               // position of that end in the first window (-1: window not complete yet)
 	long long polls = 0;
-	if (d.dbg & 16)
-		prior = (unsigned long long) k * 3600ull;
-	for (int j = (d.dbg & 16) ? -1 : k - 1; j >= 0;) {
-		unsigned long long val[LB_PER_LANE];
-#pragma unroll
-		for (int u = 0; u < LB_PER_LANE; u++) {
-			const int idx = j - (u * 64 + lane);
-			val[u] = (idx >= 0) ? __hip_atomic_load(&d.status[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : LB_FLAG_END;
-		}
-		// position (in look-back order) of the nearest row that knows its end; every row nearer must have a length
-		int first_end = 64 * LB_PER_LANE;
-		bool hole = false;
-		unsigned long long sum = 0;
-#pragma unroll
-		for (int u = LB_PER_LANE - 1; u >= 0; u--) {
-			const uint64_t m_end = __ballot((val[u] >> 62) == 2);
-			if (m_end != 0)
-				first_end = u * 64 + __builtin_ctzll(m_end);
-		}
-#pragma unroll
-		for (int u = 0; u < LB_PER_LANE; u++) {
-			const int pos = u * 64 + lane;
-			const bool counts = pos <= first_end;
-			hole = hole || (counts && (val[u] >> 62) == 0);
-			sum += counts ? (val[u] & LB_VALUE) : 0ull;
-		}
-		if (__ballot(hole) != 0) {          // a row in between has not published its length yet: look again
+	for (int j = k; j >= 0;) {
+		const int idx = j - lane;
+		const unsigned long long val = (idx >= 0) ? __hip_atomic_load(&d.status[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : LB_FLAG_END;
+		const uint64_t m_end = __ballot((val >> 62) == 2);
+		const int first_end = m_end ? __builtin_ctzll(m_end) : 64;
+		const bool counts = lane <= first_end;
+		if (__ballot(counts && (val >> 62) == 0) != 0) {          // a row in between has not published its length yet
+			if (!wait)
+				return false;
 			if (++polls > (1ll << 24)) {
 				lost = true;
 				break;
@@ -791,25 +781,64 @@ __device__ __forceinline__ unsigned long long lookback_offset(const ApplyArgs &d
 			__builtin_amdgcn_s_sleep(2);
 			continue;
 		}
-		// wave-wide sum (64-bit, two halves through DPP-free shuffles)
-		for (int sft = 32; sft >= 1; sft >>= 1) {
-			const uint32_t lo32 = (uint32_t) __shfl_xor((int) (uint32_t) sum, sft);
-			const uint32_t hi32 = (uint32_t) __shfl_xor((int) (uint32_t) (sum >> 32), sft);
-			sum += ((unsigned long long) hi32 << 32) | lo32;
+		unsigned long long v = counts ? (val & LB_VALUE) : 0ull;
+		if (near_end < 0) {
+			near_end = first_end;
+			near = (lane < first_end) ? v : 0ull;
 		}
-		prior += sum;
-		if (first_end < 64 * LB_PER_LANE)
+		for (int sft = 32; sft >= 1; sft >>= 1) {
+			const uint32_t lo32 = (uint32_t) __shfl_xor((int) (uint32_t) v, sft);
+			const uint32_t hi32 = (uint32_t) __shfl_xor((int) (uint32_t) (v >> 32), sft);
+			v += ((unsigned long long) hi32 << 32) | lo32;
+		}
+		total += v;
+		if (first_end < 64)
 			break;
-		j -= 64 * LB_PER_LANE;
+		j -= 64;
 	}
+	end = total;
+	if (!lost && near_end > 0) {
+		// the end of row k - lane is `total` less the lengths of the rows after it (the lanes before this one)
+		unsigned long long incl = near;
+		for (int sft = 1; sft < 64; sft <<= 1) {
+			const uint32_t lo32 = (uint32_t) __shfl_up((int) (uint32_t) incl, sft);
+			const uint32_t hi32 = (uint32_t) __shfl_up((int) (uint32_t) (incl >> 32), sft);
+			if (lane >= sft)
+				incl += ((unsigned long long) hi32 << 32) | lo32;
+		}
+		if (lane < near_end)
+			__hip_atomic_store(&d.status[k - lane], LB_FLAG_END | ((total - (incl - near)) & LB_VALUE), __ATOMIC_RELAXED,
+			                   __HIP_MEMORY_SCOPE_AGENT);
+	}
+	return true;
+}
+
+// The header of row k of `count` entries, whose look back gave `end`: Sp[k], Sp[nrows] behind the last row, the overflow bit.
+// Returns whether the row fits Sj / Sx; off = where it starts.
+__device__ __forceinline__ bool lb_row_header(const ApplyArgs &d, int k, int count, unsigned long long end, bool lost, int lane, int64_t &off)
+{
+	off = (int64_t) (end - (unsigned long long) count);
+	const bool fits = !lost && end <= (unsigned long long) d.cap;
 	if (lane == 0) {
-		__hip_atomic_store(&d.status[k], LB_FLAG_END | ((prior + (unsigned long long) count) & LB_VALUE), __ATOMIC_RELAXED,
-		                   __HIP_MEMORY_SCOPE_AGENT);
-		d.Sp[k] = (int64_t) prior;
+		d.Sp[k] = off;
 		if (k == d.a.nrows - 1)
-			d.Sp[d.a.nrows] = (int64_t) (prior + (unsigned long long) count);
+			d.Sp[d.a.nrows] = (int64_t) end;
+		if (!fits)
+			atomicOr(&d.a.ctr[CTR_STATUS], 1);
 	}
-	return prior;
+	return fits;
+}
+
+// what a wave of an apply kernel leaves in the statistics (lost: a look back gave up)
+__device__ __forceinline__ void apply_statistics(const SchurArgs &a, int lane, unsigned long long st_input, unsigned long long st_piv, int st_done, bool lost)
+{
+	if (lane == 0) {
+		if (lost)
+			atomicOr(&a.ctr[CTR_STATUS], 4);
+		atomicAdd(&a.ctr64[C64_INPUT], st_input);
+		atomicAdd(&a.ctr64[C64_ELIM], st_piv);          // rows of R combined (not the reference's count of eliminations)
+		atomicAdd(&a.ctr[a.done_ctr], st_done);
+	}
 }
 
 template <bool PACKED, bool PLAIN> __global__ __launch_bounds__(512) void bs_apply_kernel(ApplyArgs d)
@@ -830,6 +859,7 @@ template <bool PACKED, bool PLAIN> __global__ __launch_bounds__(512) void bs_app
 	const int64_t ldw = d.ldR / CPL;
 	unsigned long long st_input = 0, st_piv = 0;
 	int st_done = 0;
+	bool lost = false;
 
 	for (int k = blockIdx.x * d.waves + wave;; k += gridDim.x * d.waves) {
 		if (d.direct)
@@ -936,14 +966,12 @@ template <bool PACKED, bool PLAIN> __global__ __launch_bounds__(512) void bs_app
 		int *out_j = a.pool_j, *out_x = a.pool_x;
 		bool fits;
 		if (d.direct) {
-			bool lost = false;
-			const unsigned long long prior = lookback_offset(d, k, count, lane, lost);
-			if (lane == 0 && lost)
-				atomicOr(&a.ctr[CTR_STATUS], 4);
-			off = (int64_t) prior;
+			unsigned long long end = 0;
+			lb_publish_length(d, k, count, lane);
+			lookback_probe(d, k, lane, true, end, lost);
+			fits = lb_row_header(d, k, count, end, lost, lane, off);
 			out_j = d.Sj;
 			out_x = d.Sx;
-			fits = !lost && off + count <= d.cap;
 		} else {
 			unsigned long long got = 0;
 			if (lane == 0)
@@ -984,25 +1012,18 @@ template <bool PACKED, bool PLAIN> __global__ __launch_bounds__(512) void bs_app
 				}
 			}
 		}
-		if (lane == 0) {
+		if (lane == 0 && !d.direct) {          // (lb_row_header has written the header of a direct row)
 			if (fits) {
-				if (!d.direct) {
-					a.row_off[k] = off | (1LL << 62);       // sorted by column already
-					a.row_len[k] = count;
-				}
+				a.row_off[k] = off | (1LL << 62);       // sorted by column already
+				a.row_len[k] = count;
 			} else {
 				atomicOr(&a.ctr[CTR_STATUS], 1);
-				if (!d.direct)
-					a.row_len[k] = -1;
+				a.row_len[k] = -1;
 			}
 		}
 		st_done += fits ? 1 : 0;
 	}
-	if (lane == 0) {
-		atomicAdd(&a.ctr64[C64_INPUT], st_input);
-		atomicAdd(&a.ctr64[C64_ELIM], st_piv);          // rows of R combined (not the reference's count of eliminations)
-		atomicAdd(&a.ctr[a.done_ctr], st_done);
-	}
+	apply_statistics(a, lane, st_input, st_piv, st_done, lost);
 }
 
 // The same with signed 16-bit entries (SgnDev):
@@ -1142,6 +1163,17 @@ __device__ __forceinline__ int s16_reduce_segment(const ApplyArgs &d, const Mont
 	return count;
 }
 
+// entries of the packed words xw[0 .. nwords) (a segment that s16_reduce_segment did not sweep)
+__device__ __forceinline__ int s16_count_entries(const uint32_t *xw, int nwords, int lane)
+{
+	int count = 0;
+	for (int t0 = 0; t0 < nwords; t0 += 64) {
+		const uint32_t w = xw[t0 + lane];
+		count += __popcll(__ballot((w & 0xFFFFu) != 0)) + __popcll(__ballot((w >> 16) != 0));
+	}
+	return count;
+}
+
 __global__ __launch_bounds__(512) void bs_apply_s16_kernel(ApplyArgs d)
 {
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
@@ -1162,11 +1194,11 @@ __global__ __launch_bounds__(512) void bs_apply_s16_kernel(ApplyArgs d)
 	const int2 *q2 = reinterpret_cast<const int2 *>(a.q);          // (the array is padded to whole tile groups)
 	unsigned long long st_input = 0, st_piv = 0;
 	int st_done = 0;
+	bool lost = false;
 
 	for (int k = blockIdx.x * d.waves + wave;; k += gridDim.x * d.waves) {
-		if (d.direct) {
+		if (d.direct)
 			k = next_ticket(d, lane);
-		}
 		if (k >= a.nrows)
 			break;
 		const int i = a.rows[k];
@@ -1191,13 +1223,8 @@ __global__ __launch_bounds__(512) void bs_apply_s16_kernel(ApplyArgs d)
 			st_done += 1;
 			continue;
 		}
-		if (count < 0) {                     // no pivotal entry in the last batch: the segment was not swept
-			count = 0;
-			for (int t0 = 0; t0 < nwords; t0 += 64) {
-				const uint32_t w = xw[t0 + lane];
-				count += __popcll(__ballot((w & 0xFFFFu) != 0)) + __popcll(__ballot((w >> 16) != 0));
-			}
-		}
+		if (count < 0)                       // no pivotal entry in the last batch: the segment was not swept
+			count = s16_count_entries(xw, nwords, lane);
 		total += count;
 		if (d.stage != nullptr) {
 			uint32_t *out = d.stage + (int64_t) k * nwords_row + w0;
@@ -1217,14 +1244,12 @@ __global__ __launch_bounds__(512) void bs_apply_s16_kernel(ApplyArgs d)
 		int *out_j = a.pool_j, *out_x = a.pool_x;
 		bool fits;
 		if (d.direct) {
-			bool lost = false;
-			const unsigned long long prior = lookback_offset(d, k, count, lane, lost);
-			if (lane == 0 && lost)
-				atomicOr(&a.ctr[CTR_STATUS], 4);
-			off = (int64_t) prior;
+			unsigned long long end = 0;
+			lb_publish_length(d, k, count, lane);
+			lookback_probe(d, k, lane, true, end, lost);
+			fits = lb_row_header(d, k, count, end, lost, lane, off);
 			out_j = d.Sj;
 			out_x = d.Sx;
-			fits = !lost && off + count <= d.cap;
 		} else {
 			unsigned long long got = 0;
 			if (lane == 0)
@@ -1260,369 +1285,242 @@ __global__ __launch_bounds__(512) void bs_apply_s16_kernel(ApplyArgs d)
 				wpos += (uint32_t) (__popcll(m0) + __popcll(m1));
 			}
 		}
-		if (lane == 0) {
+		if (lane == 0 && !d.direct) {          // (lb_row_header has written the header of a direct row)
 			if (fits) {
-				if (!d.direct) {
-					a.row_off[k] = off | (1LL << 62);       // sorted by column already
-					a.row_len[k] = count;
-				}
+				a.row_off[k] = off | (1LL << 62);       // sorted by column already
+				a.row_len[k] = count;
 			} else {
 				atomicOr(&a.ctr[CTR_STATUS], 1);
-				if (!d.direct)
-					a.row_len[k] = -1;
+				a.row_len[k] = -1;
 			}
 		}
 		st_done += fits ? 1 : 0;
 	  }          // segments
 	}
-	if (lane == 0) {
-		atomicAdd(&a.ctr64[C64_INPUT], st_input);
-		atomicAdd(&a.ctr64[C64_ELIM], st_piv);
-		atomicAdd(&a.ctr[a.done_ctr], st_done);
-	}
+	apply_statistics(a, lane, st_input, st_piv, st_done, lost);
 }
 
 // ---- CSR output straight from the apply (signed 16-bit entries, rows of one segment) ---------------------------------------
-// bs_apply_s16_csr_kernel writes every row of S at its final place in Sj / Sx, without the staging pass below.  Each wave owns
-// TWO row buffers.  A finished row publishes its length (look-back status word, as the `direct` output above) and stays in its
-// buffer while the wave computes the next row; at every row boundary the wave takes ONE look, without waiting, whether the
-// offset of its older pending row is known (every row before it has published its length), and once it is, writes that row
-// from LDS.  A wave waits only when both buffers hold rows whose offsets are unknown, and at the end of the batch.  (The
-// `direct` output made every row wait for its slowest running predecessor with its LDS held: a third of its time on mk13.b5.)
+// bs_apply_s16_csr_kernel writes every row of S at its final place in Sj / Sx, without the staging pass below.  A wave computes
+// a row in its LDS row buffer; the finished row publishes its length (look-back status word, as the `direct` output above) and
+// stays PENDING while the wave computes the next row: at every row boundary the wave takes ONE look, without waiting, whether
+// the offset of its older pending row is known (every row before it has published its length), and once it is, writes that
+// row.  A wave waits only when two rows are pending, and at the end of the batch.  (The `direct` output makes every row wait
+// for its slowest running predecessor with its LDS held: a third of its time on mk13.b5.)  Where the older pending row waits
+// is a policy (PendingLds, PendingRegs below).
 constexpr int CSR_SCRATCH_BYTES = 512 * 4;          // per wave: the list of pivotal entries while a row is computed, the
                                                     // compaction area of the output (512 ints) while a row is written
 static_assert(CSR_SCRATCH_BYTES >= AP_LIST * (int) sizeof(uint2), "the list shares the compaction area");
 
-// One look back from row k (its length published): the status words of row k and the 63 rows before it, then further back
-// while no end is found.  true: end = offset past row k.  false: a row in between has not published its length yet -- only
-// without `wait`; with it the look is repeated (after 2^24 polls `lost` is set and true returned).  A look that succeeds also
-// publishes the ends of the rows of its first window that had only their lengths, so that the next look stops close by.
-__device__ __forceinline__ bool lookback_probe(const ApplyArgs &d, int k, int lane, bool wait, unsigned long long &end, bool &lost)
+// One tile group of a row to oj / ox from entry wpos on: word(u) is the packed word of this lane in tile u of the group
+// (u an integral constant), qq the two columns it holds.  As bs_expand_kernel, the entries of the four tiles are compacted in
+// LDS and leave in stores of 64 consecutive entries -- here through ONE area: the columns first, then the values.
+// Lane l of a tile holds columns 2 (t0 + l) and 2 (t0 + l) + 1: entries come out sorted by column.
+template <typename WordAt>
+__device__ __forceinline__ void csr_emit_group(WordAt &&word, const int2 (&qq)[AP_TU], const SgnDev &G, int *cbuf, int *oj, int *ox, uint32_t &wpos, int lane)
 {
-	unsigned long long total = 0, near = 0;          // near: length of this lane's row in the first window (rows before its nearest end)
-	int near_end = -1;                               // position of that end in the first window (-1: window not complete yet)
-	long long polls = 0;
-	for (int j = k; j >= 0;) {
-		const int idx = j - lane;
-		const unsigned long long val = (idx >= 0) ? __hip_atomic_load(&d.status[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : LB_FLAG_END;
-		const uint64_t m_end = __ballot((val >> 62) == 2);
-		const int first_end = m_end ? __builtin_ctzll(m_end) : 64;
-		const bool counts = lane <= first_end;
-		if (__ballot(counts && (val >> 62) == 0) != 0) {          // a row in between has not published its length yet
-			if (!wait)
-				return false;
-			if (++polls > (1ll << 24)) {
-				lost = true;
-				break;
-			}
-			__builtin_amdgcn_s_sleep(2);
-			continue;
-		}
-		unsigned long long v = counts ? (val & LB_VALUE) : 0ull;
-		if (near_end < 0) {
-			near_end = first_end;
-			near = (lane < first_end) ? v : 0ull;
-		}
-		for (int sft = 32; sft >= 1; sft >>= 1) {
-			const uint32_t lo32 = (uint32_t) __shfl_xor((int) (uint32_t) v, sft);
-			const uint32_t hi32 = (uint32_t) __shfl_xor((int) (uint32_t) (v >> 32), sft);
-			v += ((unsigned long long) hi32 << 32) | lo32;
-		}
-		total += v;
-		if (first_end < 64)
-			break;
-		j -= 64;
+	int v0[AP_TU], v1[AP_TU];
+	uint32_t dst[AP_TU], gpos = 0;
+	bs_static_for<0, AP_TU>([&](auto uu) {
+		constexpr int u = decltype(uu)::value;
+		sgn_unpack(word(uu), v0[u], v1[u]);
+		v0[u] = sgn_canonical(v0[u], G);
+		v1[u] = sgn_canonical(v1[u], G);
+		const uint64_t m0 = __ballot(v0[u] != 0), m1 = __ballot(v1[u] != 0);
+		uint32_t at = gpos;
+		at = __builtin_amdgcn_mbcnt_hi((uint32_t) (m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m0, at));
+		at = __builtin_amdgcn_mbcnt_hi((uint32_t) (m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m1, at));
+		dst[u] = at;
+		if (v0[u] != 0)
+			cbuf[at] = qq[u].x;
+		if (v1[u] != 0)
+			cbuf[at + (v0[u] != 0 ? 1u : 0u)] = qq[u].y;
+		gpos += (uint32_t) (__popcll(m0) + __popcll(m1));
+	});
+	for (uint32_t t = lane; t < gpos; t += 64)
+		oj[wpos + t] = cbuf[t];
+#pragma unroll
+	for (int u = 0; u < AP_TU; u++) {
+		if (v0[u] != 0)
+			cbuf[dst[u]] = v0[u];
+		if (v1[u] != 0)
+			cbuf[dst[u] + (v0[u] != 0 ? 1u : 0u)] = v1[u];
 	}
-	end = total;
-	if (!lost && near_end > 0) {
-		// the end of row k - lane is `total` less the lengths of the rows after it (the lanes before this one)
-		unsigned long long incl = near;
-		for (int sft = 1; sft < 64; sft <<= 1) {
-			const uint32_t lo32 = (uint32_t) __shfl_up((int) (uint32_t) incl, sft);
-			const uint32_t hi32 = (uint32_t) __shfl_up((int) (uint32_t) (incl >> 32), sft);
-			if (lane >= sft)
-				incl += ((unsigned long long) hi32 << 32) | lo32;
-		}
-		if (lane < near_end)
-			__hip_atomic_store(&d.status[k - lane], LB_FLAG_END | ((total - (incl - near)) & LB_VALUE), __ATOMIC_RELAXED,
-			                   __HIP_MEMORY_SCOPE_AGENT);
-	}
-	return true;
+	for (uint32_t t = lane; t < gpos; t += 64)
+		ox[wpos + t] = cbuf[t];
+	wpos += gpos;
 }
 
-// Rows are handed out by next_ticket(); every workgroup of the grid must be resident (the launcher sees to it).  LDS per wave:
-// CSR_SCRATCH_BYTES, then the two row buffers of Smpad / 2 words.
-__global__ __launch_bounds__(512) void bs_apply_s16_csr_kernel(ApplyArgs d)
+// The next row of the batch into the row buffer xw (nwords words: the whole row), its length published.  Returns the row
+// (>= nrows: none left), count = its entries.
+template <bool DEEP>
+__device__ __forceinline__ int csr_produce_row(const ApplyArgs &d, const MontDev &F, const SgnDev &G, int nwords, uint2 *plist, uint32_t *xw, int lane,
+                                               int &count, unsigned long long &st_input, unsigned long long &st_piv)
 {
-	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
-	const SchurArgs &a = d.a;
-	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-	const MontDev F = a.F;
-	const SgnDev G = d.G;
-	const int nwords = d.Smpad / 2;                      // the whole row: one segment (a multiple of 64 * AP_TU)
-	unsigned char *area = lds_raw + (size_t) wave * d.wave_bytes;
-	uint2 *plist = reinterpret_cast<uint2 *>(area);
-	int *cbuf = reinterpret_cast<int *>(area);           // (the list is not in use while a row is written)
-	uint32_t *x0 = reinterpret_cast<uint32_t *>(area + CSR_SCRATCH_BYTES), *x1 = x0 + nwords;
-	const int2 *q2 = reinterpret_cast<const int2 *>(a.q) + lane;          // (the array is padded to whole tile groups)
-	unsigned long long st_input = 0, st_piv = 0;
-	int st_done = 0;
-	bool lost = false;
-	// rows whose offset was not known yet, oldest first (-1: none; wave-uniform): k0 in x0, k1 in x1
-	int k0 = -1, c0 = 0, k1 = -1, c1 = 0;
-
-	// row k0 to Sj / Sx once its offset is known (one look, or looks until it is with `wait`); false: not known yet
-	auto settle = [&](bool wait) -> bool {
-		unsigned long long end = 0;
-		if (!lookback_probe(d, k0, lane, wait, end, lost))
-			return false;
-		const int64_t off = (int64_t) (end - (unsigned long long) c0);
-		const bool fits = !lost && end <= (unsigned long long) d.cap;
-		if (lane == 0) {
-			d.Sp[k0] = off;
-			if (k0 == a.nrows - 1)
-				d.Sp[a.nrows] = (int64_t) end;
-			if (!fits)
-				atomicOr(&a.ctr[CTR_STATUS], 1);
-		}
-		if (fits && c0 > 0) {
-			// as bs_expand_kernel: the entries of four tiles are compacted in LDS and leave in stores of 64 consecutive entries
-			// (columns first, then values through the same area); the columns of the next eight tiles are in flight during the stores
-			int *oj = d.Sj + off, *ox = d.Sx + off;
-			const int last = nwords - 64 * AP_TU;
-			uint32_t wpos = 0;
-			int2 qa[AP_TU], qb[AP_TU], qc[AP_TU];
-			auto issue = [&](int t0, int2 (&qq)[AP_TU]) {
-				const int t = (t0 < last) ? t0 : last;
-#pragma unroll
-				for (int u = 0; u < AP_TU; u++)
-					qq[u] = q2[t + 64 * u];
-			};
-			// lane l of a tile holds columns 2 (t0 + l) and 2 (t0 + l) + 1: entries come out sorted by column
-			auto emit = [&](int t0, const int2 (&qq)[AP_TU]) {
-				int v0[AP_TU], v1[AP_TU];
-				uint32_t dst[AP_TU], gpos = 0;
-#pragma unroll
-				for (int u = 0; u < AP_TU; u++) {
-					sgn_unpack(x0[t0 + 64 * u + lane], v0[u], v1[u]);
-					v0[u] = sgn_canonical(v0[u], G);
-					v1[u] = sgn_canonical(v1[u], G);
-					const uint64_t m0 = __ballot(v0[u] != 0), m1 = __ballot(v1[u] != 0);
-					uint32_t at = gpos;
-					at = __builtin_amdgcn_mbcnt_hi((uint32_t) (m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m0, at));
-					at = __builtin_amdgcn_mbcnt_hi((uint32_t) (m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m1, at));
-					dst[u] = at;
-					if (v0[u] != 0)
-						cbuf[at] = qq[u].x;
-					if (v1[u] != 0)
-						cbuf[at + (v0[u] != 0 ? 1u : 0u)] = qq[u].y;
-					gpos += (uint32_t) (__popcll(m0) + __popcll(m1));
-				}
-				for (uint32_t t = lane; t < gpos; t += 64)
-					oj[wpos + t] = cbuf[t];
-#pragma unroll
-				for (int u = 0; u < AP_TU; u++) {
-					if (v0[u] != 0)
-						cbuf[dst[u]] = v0[u];
-					if (v1[u] != 0)
-						cbuf[dst[u] + (v0[u] != 0 ? 1u : 0u)] = v1[u];
-				}
-				for (uint32_t t = lane; t < gpos; t += 64)
-					ox[wpos + t] = cbuf[t];
-				wpos += gpos;
-			};
-			constexpr int GW = 64 * AP_TU;          // words of a group
-			issue(0, qa);
-			issue(GW, qb);
-			for (int t0 = 0; t0 < nwords; t0 += 3 * GW) {
-				issue(t0 + 2 * GW, qc);
-				emit(t0, qa);
-				issue(t0 + 3 * GW, qa);
-				if (t0 + GW < nwords)
-					emit(t0 + GW, qb);
-				issue(t0 + 4 * GW, qb);
-				if (t0 + 2 * GW < nwords)
-					emit(t0 + 2 * GW, qc);
-			}
-		}
-		st_done += fits ? 1 : 0;
-		k0 = k1;
-		c0 = c1;
-		k1 = -1;
-		uint32_t *const t = x0;
-		x0 = x1;
-		x1 = t;
-		return true;
-	};
-
-	for (;;) {
-		if (k0 >= 0)
-			settle(k1 >= 0);               // one look; with both buffers taken, until the older row is written
-		const int k = next_ticket(d, lane);
-		if (k >= a.nrows)
-			break;
-		uint32_t *xw = (k0 < 0) ? x0 : x1;
-		const int i = a.rows[k];
-		const int64_t lo = a.Ap[i], hi = a.Ap[i + 1];
-		st_input += (unsigned long long) (hi - lo);
-		int count = s16_reduce_segment<true>(d, F, G, lo, hi, 0, nwords, plist, xw, lane, true, st_piv);
-		if (count < 0) {                     // no pivotal entry in the last batch: the row was not swept
-			count = 0;
-			for (int t0 = 0; t0 < nwords; t0 += 64) {
-				const uint32_t w = xw[t0 + lane];
-				count += __popcll(__ballot((w & 0xFFFFu) != 0)) + __popcll(__ballot((w >> 16) != 0));
-			}
-		}
-		if (lane == 0)
-			__hip_atomic_store(&d.status[k], LB_FLAG_LEN | (unsigned long long) count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-		if (k0 < 0) {
-			k0 = k;
-			c0 = count;
-		} else {
-			k1 = k;
-			c1 = count;
-		}
-	}
-	while (k0 >= 0)
-		settle(true);
-	if (lane == 0) {
-		if (lost)
-			atomicOr(&a.ctr[CTR_STATUS], 4);
-		atomicAdd(&a.ctr64[C64_INPUT], st_input);
-		atomicAdd(&a.ctr64[C64_ELIM], st_piv);
-		atomicAdd(&a.ctr[a.done_ctr], st_done);
-	}
+	const int k = next_ticket(d, lane);
+	if (k >= d.a.nrows)
+		return k;
+	const int i = d.a.rows[k];
+	const int64_t lo = d.a.Ap[i], hi = d.a.Ap[i + 1];
+	st_input += (unsigned long long) (hi - lo);
+	count = s16_reduce_segment<DEEP>(d, F, G, lo, hi, 0, nwords, plist, xw, lane, true, st_piv);
+	if (count < 0)                       // no pivotal entry in the last batch: the row was not swept
+		count = s16_count_entries(xw, nwords, lane);
+	lb_publish_length(d, k, count, lane);
+	return k;
 }
 
-// The same with ONE row buffer per wave: the older pending row (length published, offset not known yet) waits in a static
-// register file, one packed word per lane and tile, instead of a second LDS buffer -- half the LDS per wave, so twice the waves
-// on a CU (mk13.b5: 12 KB against 22 KB).  NT = 64-word tiles of a row (Smpad = 128 NT columns, a multiple of AP_TU).  The
-// state machine is the one above with "x0" = the register file and "x1" = the LDS buffer: a row is always computed in LDS; at
-// the next turn it is handed over to the registers (NT ds_reads at static indices), after the row that waited there has been
-// settled -- with `wait` exactly where the kernel above waits with both buffers taken.  Every index into the register file is
-// a compile-time constant (the emit loop is unrolled over the tile groups): a dynamic one would turn the file into scratch.
-// DEEP: as s16_reduce_segment.  WPE: waves per SIMD the register allocation must leave room for.
+// Where the older pending row of a wave waits.  A policy sets up the row buffers of the wave (`rows`: its LDS past the scratch
+// area; xc = the buffer rows are computed in), hands the row in xc over to the pending place, and sweeps the pending row for
+// the output: emit(word, qq) once per tile group, in order, word and qq as csr_emit_group takes them.  The columns of the next
+// two groups are in flight during the stores of a group.
+//
+// PendingLds: a second LDS buffer (LDS per wave: CSR_SCRATCH_BYTES, then two buffers of Smpad / 2 words); the hand-over swaps
+// the two.  Rows of any width that fits.
+struct PendingLds {
+	int nwords;                                          // the whole row: one segment (a multiple of 64 * AP_TU)
+	uint32_t *xc, *xp;
+
+	__device__ __forceinline__ PendingLds(const ApplyArgs &d, uint32_t *rows) : nwords(d.Smpad / 2), xc(rows), xp(rows + d.Smpad / 2) {}
+
+	__device__ __forceinline__ void hand_over(int)
+	{
+		uint32_t *const t = xp;
+		xp = xc;
+		xc = t;
+	}
+
+	template <typename Emit> __device__ __forceinline__ void sweep(const int *q, int lane, Emit &&emit)
+	{
+		constexpr int GW = 64 * AP_TU;          // words of a group
+		const int2 *q2 = reinterpret_cast<const int2 *>(q) + lane;          // (the array is padded to whole tile groups)
+		const int last = nwords - GW;
+		int2 qa[AP_TU], qb[AP_TU], qc[AP_TU];
+		// (no branch around an issue: past the end the last group is read again)
+		auto issue = [&](int t0, int2 (&qq)[AP_TU]) {
+			const int t = (t0 < last) ? t0 : last;
+#pragma unroll
+			for (int u = 0; u < AP_TU; u++)
+				qq[u] = q2[t + 64 * u];
+		};
+		auto group = [&](int t0, const int2 (&qq)[AP_TU]) {
+			emit([&](auto uu) -> uint32_t { return xp[t0 + 64 * decltype(uu)::value + lane]; }, qq);
+		};
+		issue(0, qa);
+		issue(GW, qb);
+		for (int t0 = 0; t0 < nwords; t0 += 3 * GW) {
+			issue(t0 + 2 * GW, qc);
+			group(t0, qa);
+			issue(t0 + 3 * GW, qa);
+			if (t0 + GW < nwords)
+				group(t0 + GW, qb);
+			issue(t0 + 4 * GW, qb);
+			if (t0 + 2 * GW < nwords)
+				group(t0 + 2 * GW, qc);
+		}
+	}
+};
+
+// PendingRegs<NT>: a static register file, one packed word per lane and tile -- half the LDS per wave, so twice the waves on a
+// CU (mk13.b5: 12 KB against 22 KB).  NT = 64-word tiles of a row (Smpad = 128 NT columns, a multiple of AP_TU).  The hand-over
+// is NT ds_reads at static indices.  Every index into the register file is a compile-time constant (the sweep is unrolled over
+// the tile groups): a dynamic one would turn the file into scratch.
 constexpr int CSR_ROWREG_MAX_TILES = 40;            // widest instantiation: Smpad = 5,120 columns, 40 registers
 constexpr bool CSR_ROWREG_DEEP = false;
 constexpr int CSR_ROWREG_WPE = 4;
 
-template <int NT, bool DEEP, int WPE>
-__global__ __launch_bounds__(512, WPE) void bs_apply_s16_csr_rowreg_kernel(ApplyArgs d)
-{
+template <int NT> struct PendingRegs {
 	static_assert(NT % AP_TU == 0 && NT >= AP_TU && NT <= CSR_ROWREG_MAX_TILES, "whole tile groups");
+	static constexpr int nwords = 64 * NT;               // the whole row: one segment
+	uint32_t *xc;
+	RegFile<uint32_t, NT> xr;
+
+	__device__ __forceinline__ PendingRegs(const ApplyArgs &, uint32_t *rows) : xc(rows) {}
+
+	__device__ __forceinline__ void hand_over(int lane)
+	{
+		bs_static_for<0, NT>([&](auto tt) {
+			constexpr int t = decltype(tt)::value;
+			xr.template at<t>() = xc[64 * t + lane];
+		});
+	}
+
+	template <typename Emit> __device__ __forceinline__ void sweep(const int *q, int lane, Emit &&emit)
+	{
+		constexpr int NG = NT / AP_TU;          // tile groups of a row
+		constexpr int GW = 64 * AP_TU;          // words of a group
+		int2 qa[AP_TU], qb[AP_TU], qc[AP_TU];
+		// (the byte offset of a group goes through an empty asm: as constants, the 64-bit addresses of every group would be
+		//  formed once before the loop over the rows and held in two registers each)
+		auto issue = [&](int t0, int2 (&qq)[AP_TU]) {
+			uint32_t at = (uint32_t) (t0 + lane) * (uint32_t) sizeof(int2);
+			asm volatile("" : "+v"(at));
+			const int2 *qg = reinterpret_cast<const int2 *>(reinterpret_cast<const char *>(q) + at);
+#pragma unroll
+			for (int u = 0; u < AP_TU; u++)
+				qq[u] = qg[64 * u];
+		};
+		issue(0, qa);
+		if constexpr (NG > 1)
+			issue(GW, qb);
+		bs_static_for<0, NG>([&](auto gg) {
+			constexpr int g = decltype(gg)::value;
+			auto word = [&](auto uu) -> uint32_t { return xr.template at<g * AP_TU + decltype(uu)::value>(); };
+			if constexpr (g % 3 == 0) {
+				if constexpr (g + 2 < NG)
+					issue((g + 2) * GW, qc);
+				emit(word, qa);
+			} else if constexpr (g % 3 == 1) {
+				if constexpr (g + 2 < NG)
+					issue((g + 2) * GW, qa);
+				emit(word, qb);
+			} else {
+				if constexpr (g + 2 < NG)
+					issue((g + 2) * GW, qb);
+				emit(word, qc);
+			}
+		});
+	}
+};
+
+// Rows are handed out by next_ticket(); every workgroup of the grid must be resident (the launcher sees to it).
+// DEEP: as s16_reduce_segment.  WPE: waves per SIMD the register allocation must leave room for (0: no bound).
+template <typename Pending, bool DEEP, int WPE>
+__global__ __launch_bounds__(512, WPE) void bs_apply_s16_csr_kernel(ApplyArgs d)
+{
 	extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
 	const SchurArgs &a = d.a;
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 	const MontDev F = a.F;
 	const SgnDev G = d.G;
-	constexpr int nwords = 64 * NT;                      // the whole row: one segment
-	constexpr int NG = NT / AP_TU;                       // tile groups of a row
-	constexpr int GW = 64 * AP_TU;                       // words of a group
 	unsigned char *area = lds_raw + (size_t) wave * d.wave_bytes;
 	uint2 *plist = reinterpret_cast<uint2 *>(area);
 	int *cbuf = reinterpret_cast<int *>(area);           // (the list is not in use while a row is written)
-	uint32_t *xl = reinterpret_cast<uint32_t *>(area + CSR_SCRATCH_BYTES);
+	Pending pend(d, reinterpret_cast<uint32_t *>(area + CSR_SCRATCH_BYTES));
 	unsigned long long st_input = 0, st_piv = 0;
 	int st_done = 0;
 	bool lost = false;
-	// rows whose offset was not known yet (-1: none; wave-uniform): k0 in the register file (the older one), k1 in the LDS buffer
-	RegFile<uint32_t, NT> xr;
+	// rows whose offset was not known yet (-1: none; wave-uniform): k0 in the pending place (the older one), k1 in the buffer xc
 	int k0 = -1, c0 = 0, k1 = -1, c1 = 0;
 
-	// row k0 to Sj / Sx once its offset is known (one look, or looks until it is with `wait`); false: not known yet
-	auto settle = [&](bool wait) -> bool {
+	// row k0 to Sj / Sx once its offset is known (one look, or looks until it is with `wait`)
+	auto settle = [&](bool wait) {
 		unsigned long long end = 0;
 		if (!lookback_probe(d, k0, lane, wait, end, lost))
-			return false;
-		const int64_t off = (int64_t) (end - (unsigned long long) c0);
-		const bool fits = !lost && end <= (unsigned long long) d.cap;
-		if (lane == 0) {
-			d.Sp[k0] = off;
-			if (k0 == a.nrows - 1)
-				d.Sp[a.nrows] = (int64_t) end;
-			if (!fits)
-				atomicOr(&a.ctr[CTR_STATUS], 1);
-		}
+			return;
+		int64_t off = 0;
+		const bool fits = lb_row_header(d, k0, c0, end, lost, lane, off);
 		if (fits && c0 > 0) {
-			// as in the kernel above, the words from the register file: the group index is a compile-time constant
 			int *oj = d.Sj + off, *ox = d.Sx + off;
 			uint32_t wpos = 0;
-			int2 qa[AP_TU], qb[AP_TU], qc[AP_TU];
-			// (the byte offset of a group goes through an empty asm: as constants, the 64-bit addresses of every group would be
-			//  formed once before the loop over the rows and held in two registers each)
-			auto issue = [&](int t0, int2 (&qq)[AP_TU]) {
-				uint32_t at = (uint32_t) (t0 + lane) * (uint32_t) sizeof(int2);
-				asm volatile("" : "+v"(at));
-				const int2 *qg = reinterpret_cast<const int2 *>(reinterpret_cast<const char *>(a.q) + at);
-#pragma unroll
-				for (int u = 0; u < AP_TU; u++)
-					qq[u] = qg[64 * u];
-			};
-			// lane l of a tile holds columns 2 (t0 + l) and 2 (t0 + l) + 1: entries come out sorted by column
-			auto emit = [&](auto gg, const int2 (&qq)[AP_TU]) {
-				constexpr int g = decltype(gg)::value;
-				int v0[AP_TU], v1[AP_TU];
-				uint32_t dst[AP_TU], gpos = 0;
-				bs_static_for<0, AP_TU>([&](auto uu) {
-					constexpr int u = decltype(uu)::value;
-					sgn_unpack(xr.template at<g * AP_TU + u>(), v0[u], v1[u]);
-					v0[u] = sgn_canonical(v0[u], G);
-					v1[u] = sgn_canonical(v1[u], G);
-					const uint64_t m0 = __ballot(v0[u] != 0), m1 = __ballot(v1[u] != 0);
-					uint32_t at = gpos;
-					at = __builtin_amdgcn_mbcnt_hi((uint32_t) (m0 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m0, at));
-					at = __builtin_amdgcn_mbcnt_hi((uint32_t) (m1 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m1, at));
-					dst[u] = at;
-					if (v0[u] != 0)
-						cbuf[at] = qq[u].x;
-					if (v1[u] != 0)
-						cbuf[at + (v0[u] != 0 ? 1u : 0u)] = qq[u].y;
-					gpos += (uint32_t) (__popcll(m0) + __popcll(m1));
-				});
-				for (uint32_t t = lane; t < gpos; t += 64)
-					oj[wpos + t] = cbuf[t];
-#pragma unroll
-				for (int u = 0; u < AP_TU; u++) {
-					if (v0[u] != 0)
-						cbuf[dst[u]] = v0[u];
-					if (v1[u] != 0)
-						cbuf[dst[u] + (v0[u] != 0 ? 1u : 0u)] = v1[u];
-				}
-				for (uint32_t t = lane; t < gpos; t += 64)
-					ox[wpos + t] = cbuf[t];
-				wpos += gpos;
-			};
-			// the columns of the next two groups are in flight during the stores of a group
-			issue(0, qa);
-			if constexpr (NG > 1)
-				issue(GW, qb);
-			bs_static_for<0, NG>([&](auto gg) {
-				constexpr int g = decltype(gg)::value;
-				if constexpr (g % 3 == 0) {
-					if constexpr (g + 2 < NG)
-						issue((g + 2) * GW, qc);
-					emit(gg, qa);
-				} else if constexpr (g % 3 == 1) {
-					if constexpr (g + 2 < NG)
-						issue((g + 2) * GW, qa);
-					emit(gg, qb);
-				} else {
-					if constexpr (g + 2 < NG)
-						issue((g + 2) * GW, qb);
-					emit(gg, qc);
-				}
-			});
+			pend.sweep(a.q, lane, [&](auto &&word, const int2 (&qq)[AP_TU]) { csr_emit_group(word, qq, G, cbuf, oj, ox, wpos, lane); });
 		}
 		st_done += fits ? 1 : 0;
 		k0 = -1;
-		return true;
 	};
-	// the row in the LDS buffer becomes the older pending row (the register file is free)
+	// the row in xc becomes the older pending row (the pending place is free)
 	auto hand_over = [&]() {
-		bs_static_for<0, NT>([&](auto tt) {
-			constexpr int t = decltype(tt)::value;
-			xr.template at<t>() = xl[64 * t + lane];
-		});
+		pend.hand_over(lane);
 		k0 = k1;
 		c0 = c1;
 		k1 = -1;
@@ -1638,34 +1536,16 @@ __global__ __launch_bounds__(512, WPE) void bs_apply_s16_csr_rowreg_kernel(Apply
 			hand_over();
 		if (finishing)
 			break;
-		const int k = next_ticket(d, lane);
+		int count = 0;
+		const int k = csr_produce_row<DEEP>(d, F, G, pend.nwords, plist, pend.xc, lane, count, st_input, st_piv);
 		if (k >= a.nrows) {
 			finishing = true;
 			continue;
 		}
-		const int i = a.rows[k];
-		const int64_t lo = a.Ap[i], hi = a.Ap[i + 1];
-		st_input += (unsigned long long) (hi - lo);
-		int count = s16_reduce_segment<DEEP>(d, F, G, lo, hi, 0, nwords, plist, xl, lane, true, st_piv);
-		if (count < 0) {                     // no pivotal entry in the last batch: the row was not swept
-			count = 0;
-			for (int t0 = 0; t0 < nwords; t0 += 64) {
-				const uint32_t w = xl[t0 + lane];
-				count += __popcll(__ballot((w & 0xFFFFu) != 0)) + __popcll(__ballot((w >> 16) != 0));
-			}
-		}
-		if (lane == 0)
-			__hip_atomic_store(&d.status[k], LB_FLAG_LEN | (unsigned long long) count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 		k1 = k;
 		c1 = count;
 	}
-	if (lane == 0) {
-		if (lost)
-			atomicOr(&a.ctr[CTR_STATUS], 4);
-		atomicAdd(&a.ctr64[C64_INPUT], st_input);
-		atomicAdd(&a.ctr64[C64_ELIM], st_piv);
-		atomicAdd(&a.ctr[a.done_ctr], st_done);
-	}
+	apply_statistics(a, lane, st_input, st_piv, st_done, lost);
 }
 
 // ---- staged sparse output (signed 16-bit entries) --------------------------------------------------
@@ -2621,15 +2501,15 @@ bool backsolve_stages_output(const spasm_hip_dfact *F, int64_t *row_bytes)
 	return B.planned && env_int("SPASM_HIP_BS_STAGED", 1) != 0;
 }
 
-// bytes of LDS a wave of the CSR-output kernels needs: the list / compaction area and its row buffers (two, or one beside the
-// register file of bs_apply_s16_csr_rowreg_kernel)
+// bytes of LDS a wave of bs_apply_s16_csr_kernel needs: the list / compaction area and its row buffers (two with PendingLds,
+// one beside the register file of PendingRegs)
 static size_t csr_wave_bytes(int64_t ldR, int buffers)
 {
 	return (size_t) CSR_SCRATCH_BYTES + (size_t) buffers * (size_t) ldR * 2;
 }
 
-// 64-word tiles of a row when bs_apply_s16_csr_rowreg_kernel takes the batch; 0: rows wider than its widest instantiation, or
-// SPASM_HIP_BS_CSR_ROWREG=0 (A/B runs, tests): the two-buffer kernel
+// 64-word tiles of a row when the batch goes to PendingRegs; 0: rows wider than its widest instantiation, or
+// SPASM_HIP_BS_CSR_ROWREG=0 (A/B runs, tests): PendingLds
 static int csr_rowreg_tiles(int64_t ldR)
 {
 	if (ldR > 128 * CSR_ROWREG_MAX_TILES || env_int("SPASM_HIP_BS_CSR_ROWREG", 1) == 0)
@@ -2641,8 +2521,8 @@ using CsrKernel = void (*)(ApplyArgs);
 static CsrKernel csr_kernel(int tiles)
 {
 	switch (tiles) {
-	case 0: return bs_apply_s16_csr_kernel;
-#define ROWREG_CASE(NT) case NT: return bs_apply_s16_csr_rowreg_kernel<NT, CSR_ROWREG_DEEP, CSR_ROWREG_WPE>;
+	case 0: return bs_apply_s16_csr_kernel<PendingLds, true, 0>;
+#define ROWREG_CASE(NT) case NT: return bs_apply_s16_csr_kernel<PendingRegs<NT>, CSR_ROWREG_DEEP, CSR_ROWREG_WPE>;
 	ROWREG_CASE(4) ROWREG_CASE(8) ROWREG_CASE(12) ROWREG_CASE(16) ROWREG_CASE(20)
 	ROWREG_CASE(24) ROWREG_CASE(28) ROWREG_CASE(32) ROWREG_CASE(36) ROWREG_CASE(40)
 #undef ROWREG_CASE

@@ -287,8 +287,8 @@ struct BsDirectOut {
 	int64_t cap;                  // capacity of Sj / Sx
 	// the rows of S straight from their LDS buffers to Sj / Sx (backsolve.hip: bs_apply_s16_csr_kernel), no staging buffer
 	bool csr = false;
-	int csr_tiles = -1;               // set by the launch: 64-word tiles of a row when bs_apply_s16_csr_rowreg_kernel ran (the older
-	                                  // pending row of a wave in registers), 0: the two-buffer kernel, -1: no CSR output
+	int csr_tiles = -1;               // set by the launch: 64-word tiles of a row when its PendingRegs policy ran (the older pending
+	                                  // row of a wave in registers), 0: PendingLds (two row buffers), -1: no CSR output
 	// staged output (backsolve.hip): room for stage_rows rows of R's width; nullptr: look-back output
 	uint32_t *stage = nullptr;
 	int64_t stage_rows = 0;

@@ -125,6 +125,70 @@ def test_backsolve_output_modes(oracle, monkeypatch, p, env):
     _run(oracle, monkeypatch, p, *sysm, min_pivots=1000)
 
 
+@pytest.mark.parametrize("p", [257, 65521, 4294967291])
+def test_backsolve_lookback_output_many_short_rows(oracle, monkeypatch, p):
+    """the look-back output (SPASM_HIP_BS_STAGED=0) of every arithmetic -- signed 16-bit, unsigned 16-bit, Montgomery -- on
+    20,000 short rows: rows this short finish faster than their predecessors publish their lengths, so every wave waits in
+    its look back many times.  Against the default output (CSR or staged): the same Sp, Sj and Sx, bit for bit.  With a pool
+    of half the entries both raise the overflow status and report the same total, and the workspace is intact afterwards:
+    one row that fits comes out as the oracle has it, from the same kernel on the same workspace."""
+    import torch
+    npiv = 2000
+    rng = np.random.default_rng(11)
+    n, m, ti, tj, tx = _triangular_system(rng, p, npiv=npiv, nnon=700, nred=20000, deps=lambda k: 2, reach=40, np_per_row=2, red_entries=4)
+    A = oracle.compress(p, n, m, ti, tj, tx)
+    # (the factor from the pivot rows alone: exactly 700 non-pivotal columns, and no search over the 20,000 rows to reduce)
+    top = ti < npiv
+    P = oracle.compress(p, npiv, m, ti[top], tj[top], tx[top])
+    found, _, F = oracle.pivots_extract_structural(P, oracle.empty_fact(P.n, P.m, p))
+    assert found == npiv
+    rows = np.arange(npiv, n, dtype=np.int32)
+    one = rows[1:2]
+    want_one, _, _ = oracle.schur(A, one, F)
+    assert want_one.nnz > 0
+    monkeypatch.setenv("SPASM_HIP_BACKSOLVE", "1")
+    monkeypatch.setenv("SPASM_HIP_BS_SIGNED", "1")
+    dA = spasm_amd.DeviceCsr.from_host(_as_product(A))
+
+    def run(lookback, pool):
+        """the batch on a fresh factor and workspace of `pool` entries: (S on the device or None, stats, factor, workspace)"""
+        dF = spasm_amd.DeviceFact(_fact(F))
+        W = spasm_amd.SchurWorkspace(len(rows), A.m, pool)
+        return batch(lookback, rows, dF, W) + (dF, W)
+
+    def batch(lookback, which, dF, W):
+        if lookback:
+            monkeypatch.setenv("SPASM_HIP_BS_STAGED", "0")
+        try:
+            S, st = spasm_amd.dschur(dA, torch.from_numpy(which).cuda(), dF, W)
+        finally:
+            if lookback:
+                monkeypatch.delenv("SPASM_HIP_BS_STAGED")
+        assert st.used_backsolve == 1
+        if lookback:
+            assert st.kernel_expand.decode() == ""
+        return S, st
+
+    S0, st0 = run(False, 1 << 26)[:2]
+    S1, st1 = run(True, 1 << 26)[:2]
+    assert st0.status == 0 and st1.status == 0
+    assert st0.nnz == st1.nnz and st0.nnz > 20000
+    H0, H1 = S0.to_host(), S1.to_host()
+    assert np.array_equal(H0.p, H1.p)
+    assert np.array_equal(H0.j, H1.j)
+    assert np.array_equal(H0.x, H1.x)
+
+    cap = st0.nnz // 2
+    assert want_one.nnz <= cap
+    for lookback in (False, True):
+        S, st, dF, W = run(lookback, cap)
+        assert S is None and st.status == 1 and st.nnz == st0.nnz
+        S, st = batch(lookback, one, dF, W)
+        assert st.status == 0 and st.nnz == want_one.nnz
+        H = S.to_host()
+        assert oracle.same_matrix(oracle.CSR(H.n, H.m, H.p, H.j, H.x, p), want_one)
+
+
 @pytest.mark.parametrize("signed", ["1", "0"])
 def test_backsolve_long_input_rows(oracle, monkeypatch, signed):
     """rows to reduce with hundreds of pivotal entries (more than one pass of the apply kernel's list)."""
