@@ -4,17 +4,23 @@
 // Blocked Gauss-Jordan with column-rank-profile pivots, rows stay in place:
 //   for each panel of NB columns
 //     1. panel step: k <= NB new pivots (rows rho, columns gamma) and the n x k multipliers M such that the
-//        composite row transformation of the panel is T = I + M e_rho^T.  Default: a tournament over the free
-//        rows + one Gauss-Jordan of a 64 x 128 block (see "Tournament panel step" below); the older kernels
+//        composite row transformation of the panel is T = I + M e_rho^T.  Default: a try -- the 64 x 64 block of the first 64
+//        free rows inverted in one workgroup (rref_try_inverse) --, and when that does not give 64 pivots a tournament over
+//        the free rows + one Gauss-Jordan of its 64 winners (see "Tournament panel step" below); the older kernels
 //        eliminate column by column (one workgroup, or several with a grid barrier per column);
 //     2. gather B = A[rho, rest] (the k new pivot rows, old values);
-//     3. trailing update A[:, rest] += M B  (GEMM mod p), deferred over super-panels of four panels (K <= 256).
+//     3. trailing update A[:, rest] += M B  (GEMM mod p): K = 64 at once on the columns of the panel's super-panel, deferred
+//        beyond it over super-panels of eight panels (K <= 512) on the matrix cores, of four with VALU updates.
 //        For p < 2^16 the GEMM runs on the matrix cores: operands are split into two signed base-256 digits and
 //        multiplied with v_mfma_i32_32x32x32_i8 (four digit products, i32 accumulators, recombined mod p).
 //        Larger primes use a tiled 64-bit VALU kernel.
+//   While the tries succeed a super-panel is enqueued optimistically (no selection kernels, one look at an abort word per
+//   pass), the try of panel i + 1 one panel ahead of the update of panel i on a stream of its own (rref_lookahead); the far
+//   part of a super-panel's update runs on a second stream beside the panels of the next one.  Host side: device_rref.
 // Values are canonical representatives in [0, p) stored as u32.
 #include <algorithm>
 #include <cstring>
+#include <optional>
 #include <type_traits>
 #include "device_types.h"
 #include "field_dev.h"
@@ -2046,110 +2052,315 @@ __global__ __launch_bounds__(256) void rref_tmp_to_rows(uint32_t *A, int64_t ld,
 
 // ---- driver: everything resident on the device.  On return rows 0..rank-1 of A are the reduced
 // echelon rows (pivot columns increasing, listed in d_pivcol), the other rows are zero. ----
-int device_rref(int64_t prime, int n, int m, uint32_t *dA, int64_t ld, int *d_pivcol, hipStream_t stream, int use_mfma,
-                float *ms_update)
-{
-	if (n == 0 || m == 0)
-		return 0;
-	const double t_entry = wtime();
-	// work buffers are kept between calls (per host thread; SPASM_HIP_RREF_CACHE=0: allocated and freed every time): 28
-	// hipMalloc / hipFree pairs and the half-gigabyte row buffer of the final permutation were 2 of the 11 ms of a
-	// 4096 x 32768 block, and the dense finish calls this several times in a row
-	struct Cache {
-		int dev = -1;
-		std::vector<std::pair<void *, size_t>> slots;
+namespace {
+
+// The digit planes of the matrix-core updates (rref_update_mfma_multi), set after set: Mh [n][64] | Ml [n][64] from base_M on,
+// Bh [m][64] | Bl [m][64] from base_B on.
+struct DigitPlanes {
+	signed char *base_M, *base_B;
+	size_t n, m;
+	signed char *Mh(int set) const { return base_M + (size_t) set * 2 * n * 64; }
+	signed char *Ml(int set) const { return Mh(set) + n * 64; }
+	signed char *Bh(int set) const { return base_B + (size_t) set * 2 * m * 64; }
+	signed char *Bl(int set) const { return Bh(set) + m * 64; }
+};
+
+// Work buffers of device_rref, kept between calls (per host thread; SPASM_HIP_RREF_CACHE=0, and any request above 4 GB: allocated
+// and freed by the call): 28 hipMalloc / hipFree pairs and the half-gigabyte row buffer of the final permutation were 2 of the
+// 11 ms of a 4096 x 32768 block, and the dense finish calls this several times in a row.  A slot per buffer, whichever route
+// a call takes; blocks grow by a quarter and are handed out dirty.
+struct RrefWorkspace {
+	enum Buf {
+		PIVOT_ROWS, FLAGS, PIVROW, RANK, COL_PANEL, COL_KNEW, COL_RHO, TMP,
+		// the panel buffers: given back before the final permutation takes TMP
+		CAND_A, CAND_B, FREE_COUNT, GAMMA, CAND_FIRST, FIRST64, LIVE_LIST, CAND_PIVOT, P4, BT4, RHO4, INVTAB, M8, B8, ZACC, KNEW4, FULL_FLAG, GINV,
+		ALT_TILE, PROBE, COOP_BARRIER, COOP_CAND, COOP_ERR, NBUF
 	};
-	static thread_local Cache cache;
+	struct Kept {
+		int dev = -1;
+		void *ptr[NBUF] = {};
+		size_t bytes[NBUF] = {};
+	};
+	Kept &kept;
 	const bool use_cache = sh::env_get("SPASM_HIP_RREF_CACHE") == nullptr || std::atoi(sh::env_get("SPASM_HIP_RREF_CACHE")) != 0;
-	size_t next_slot = 0;
+	void *owned[NBUF] = {};          // blocks of this call alone
+
+	static Kept &of_this_thread()
 	{
+		static thread_local Kept k;
 		int dev = 0;
 		HIP_CHECK(hipGetDevice(&dev));
-		if (cache.dev != dev) {
-			for (auto &sl : cache.slots)
-				sh::big_free(sl.first);
-			cache.slots.clear();
-			cache.dev = dev;
+		if (k.dev != dev) {
+			for (int b = 0; b < NBUF; b++)
+				if (k.ptr[b] != nullptr)
+					sh::big_free(k.ptr[b]);
+			k = Kept();
+			k.dev = dev;
+		}
+		return k;
+	}
+	RrefWorkspace() : kept(of_this_thread()) {}
+	~RrefWorkspace() { release(0); }
+	template <typename T> T *take(Buf b, size_t bytes)
+	{
+		if (!use_cache || bytes > ((size_t) 4 << 30)) {
+			HIP_CHECK(sh::malloc_or_trim(&owned[b], bytes));
+			return static_cast<T *>(owned[b]);
+		}
+		if (kept.bytes[b] < bytes) {
+			sh::big_free(kept.ptr[b]);
+			kept.ptr[b] = nullptr;          // (an allocation that fails leaves an empty slot, not a stale one)
+			kept.bytes[b] = 0;
+			HIP_CHECK(sh::malloc_or_trim(&kept.ptr[b], bytes + bytes / 4));
+			kept.bytes[b] = bytes + bytes / 4;
+		}
+		return static_cast<T *>(kept.ptr[b]);
+	}
+	void release(int first)          // the call's own blocks, from slot `first` on
+	{
+		for (int b = first; b < NBUF; b++)
+			if (owned[b] != nullptr) {
+				sh::big_free(owned[b]);
+				owned[b] = nullptr;
+			}
+	}
+};
+
+// What a call decides once, from the modulus, its arguments and the environment.
+struct RrefRoute {
+	bool tournament;          // panel step: tournament (default) or the column-by-column kernels (SPASM_HIP_RREF_PANEL=columns)
+	bool small_prime, small16;          // 2 p^2 < 2^32: the panel kernels use 24-bit multiplies; p < 2^16
+	bool mfma_ok;             // two signed base-256 digits must fit int8
+	bool fast_try;            // the 64 x 64 inversion kernel for the try: signed representatives with deferred reduction need 4 B^2 + B < 2^31, B = p/2 + p/64 + 1
+	bool two_streams;         // the far update of a super-panel on a stream of its own
+	bool use_ahead;           // one panel ahead (rref_lookahead); after rref_streams: ... and kernels of the two streams do meet
+	bool timing, timed;       // SPASM_HIP_RREF_TIMING: stages on stderr; timed: the caller asked for the time of the updates
+	int SPW;                  // panels per super-panel: eight on the matrix cores (K = 512 per pass over the matrix), four with VALU updates
+	int coop_min_rows;        // tall blocks: the column-by-column panel step is spread over several workgroups (SPASM_HIP_COOP_ROWS rows and up)
+	// one panel ahead: blocks of at most 6,144 rows: beyond, the multipliers and the update of a panel take longer than its try -- the chain is no
+	// longer what the call waits for, and two streams of kernels that poll each other only get in the way: 16,384 x 16,384 went from 40 to 53 ms with it
+	int look_rows;
+};
+
+RrefRoute rref_route(int64_t prime, int use_mfma, bool timed)
+{
+	const char *panel = sh::env_get("SPASM_HIP_RREF_PANEL"), *coop = sh::env_get("SPASM_HIP_COOP_ROWS"), *look = sh::env_get("SPASM_HIP_RREF_LOOKAHEAD");
+	const bool tournament = panel == nullptr || std::strcmp(panel, "columns") != 0;
+	const bool small_prime = prime < 46341;
+	const bool small16 = prime < 65536;
+	const bool mfma_ok = use_mfma && prime <= 65279;
+	const bool fast_try = small_prime && (4 * (prime / 2 + prime / 64 + 1) * (prime / 2 + prime / 64 + 1) + (prime / 2 + prime / 64 + 1) <= 0x7FFFFFFFll);
+	const bool two_streams = tournament && mfma_ok && !sh::env_get("SPASM_HIP_RREF_ONE_STREAM");
+	const bool use_ahead = tournament && mfma_ok && small16 && (look == nullptr || std::atoi(look) != 0);
+	return RrefRoute{tournament, small_prime, small16, mfma_ok, fast_try, two_streams, use_ahead, sh::env_get("SPASM_HIP_RREF_TIMING") != nullptr, timed, mfma_ok ? MAXSETS : 4,
+	                 coop != nullptr ? std::atoi(coop) : 2048, 6144};
+}
+
+// The second stream (far updates), the stream of the tries of a lookahead pass and their events, kept between calls (per host
+// thread, created once per device), and what handoff_probe said about the pair (main stream, try stream).
+struct RrefStreams {
+	int dev = -1;
+	hipStream_t s_try = nullptr, s_far = nullptr, probed_main = nullptr;
+	hipEvent_t ev_upd[MAXSETS] = {}, ev_look = nullptr, ev_start = nullptr, ev_near = nullptr, ev_far = nullptr;
+	bool probed = false, met = false;
+};
+
+// ... ready for a call on `stream`.  *use_ahead: in, the call would run its tries one panel ahead; out, ... and may: the hand-offs
+// need a kernel of each stream on the device at the same time, asked once per pair of streams (handoff_probe).
+RrefStreams &rref_streams(hipStream_t stream, RrefWorkspace &ws, bool *use_ahead)
+{
+	static thread_local RrefStreams st;
+	int dev = 0;
+	HIP_CHECK(hipGetDevice(&dev));
+	if (st.dev != dev) {
+		// (Tried: disjoint compute units for the two streams (hipExtStreamCreateWithCUMask: sixteen for the tries, the rest for the far
+		//  updates) -- the trace shows a try at 75-79 us instead of 44 whenever the far update of the super-panel before shares its
+		//  compute unit.  The call went from 8.3 to 16 ms: masked queues are served far more slowly on this stack.  Plain streams.)
+		HIP_CHECK(hipStreamCreateWithFlags(&st.s_far, hipStreamNonBlocking));
+		HIP_CHECK(hipStreamCreateWithFlags(&st.s_try, hipStreamNonBlocking));
+		for (int t = 0; t < MAXSETS; t++)
+			HIP_CHECK(hipEventCreateWithFlags(&st.ev_upd[t], hipEventDisableTiming));
+		HIP_CHECK(hipEventCreateWithFlags(&st.ev_look, hipEventDisableTiming));
+		HIP_CHECK(hipEventCreateWithFlags(&st.ev_start, hipEventDisableTiming));
+		HIP_CHECK(hipEventCreate(&st.ev_near));
+		HIP_CHECK(hipEventCreate(&st.ev_far));          // (with timing: a timed call measures its far updates up to this event)
+		st.probed = false;
+		st.dev = dev;
+	}
+	if (*use_ahead && (!st.probed || st.probed_main != stream)) {
+		int *pw = ws.take<int>(ws.PROBE, 4 * sizeof(int)), met[2] = {0, 0};
+		HIP_CHECK(hipMemsetAsync(pw, 0, 4 * sizeof(int), stream));
+		HIP_CHECK(hipEventRecord(st.ev_start, stream));
+		HIP_CHECK(hipStreamWaitEvent(st.s_try, st.ev_start, 0));
+		hipLaunchKernelGGL(handoff_probe, dim3(1), dim3(1), 0, stream, pw, 0, pw + 2);
+		hipLaunchKernelGGL(handoff_probe, dim3(1), dim3(1), 0, st.s_try, pw, 1, pw + 2);
+		HIP_CHECK(hipEventRecord(st.ev_look, st.s_try));
+		HIP_CHECK(hipStreamWaitEvent(stream, st.ev_look, 0));
+		HIP_CHECK(hipMemcpyAsync(met, pw + 2, sizeof(met), hipMemcpyDeviceToHost, stream));
+		HIP_CHECK(hipStreamSynchronize(stream));
+		st.probed_main = stream;
+		st.met = met[0] != 0 && met[1] != 0;
+		st.probed = true;
+		if (!st.met && sh::verbose() >= 1)
+			fprintf(stderr, "[spasm_hip] dense RREF: kernels of two streams do not run side by side here (a tool that serialises launches?): no lookahead\n");
+	}
+	*use_ahead = *use_ahead && st.met;
+	return st;
+}
+
+// The time of the trailing updates of a timed call: before() and after() around the launches, after() waits for them; no-ops in an untimed call.
+struct UpdateTimer {
+	hipEvent_t e0 = nullptr, e1 = nullptr;
+	float total = 0.f;
+	explicit UpdateTimer(bool timed)
+	{
+		if (timed) {
+			HIP_CHECK(hipEventCreate(&e0));
+			HIP_CHECK(hipEventCreate(&e1));
 		}
 	}
-	std::vector<void *> owned;
-	auto ws_malloc = [&](void **ptr, size_t bytes) {
-		if (!use_cache || bytes > ((size_t) 4 << 30)) {
-			HIP_CHECK(sh::malloc_or_trim(ptr, bytes));
-			owned.push_back(*ptr);
+	~UpdateTimer()
+	{
+		if (e0 != nullptr) {
+			(void) hipEventDestroy(e0);
+			(void) hipEventDestroy(e1);
+		}
+	}
+	void before(hipStream_t s)
+	{
+		if (e0 != nullptr)
+			HIP_CHECK(hipEventRecord(e0, s));
+	}
+	void after(hipStream_t s, hipEvent_t end = nullptr)          // end: an event already recorded behind the launches (else e1 is)
+	{
+		if (e0 == nullptr)
 			return;
+		if (end == nullptr)
+			HIP_CHECK(hipEventRecord(end = e1, s));
+		HIP_CHECK(hipEventSynchronize(end));
+		float ms;
+		HIP_CHECK(hipEventElapsedTime(&ms, e0, end));
+		total += ms;
+	}
+};
+
+// What both routes of a call work on.
+struct RrefCall {
+	uint32_t *A;          // n x m, leading dimension ld
+	int64_t ld;
+	int n, m;
+	int *pivcol, *flags, *pivrow, *rank_d;
+	uint32_t *B;          // NB x m: the pivot rows of a panel
+	hipStream_t stream;
+	MontDev F;
+	RrefRoute r;
+	UpdateTimer *timer;
+};
+
+// Column by column (SPASM_HIP_RREF_PANEL=columns): one workgroup eliminates the panel, or several with a grid barrier per column
+// (cooperative kernel, from SPASM_HIP_COOP_ROWS rows up); K = 64 update of everything to the right after every panel.
+void rref_by_columns(const RrefCall &c, RrefWorkspace &ws, int *coop_err)
+{
+	const int n = c.n, m = c.m;
+	const hipStream_t stream = c.stream;
+	uint32_t *P = ws.take<uint32_t>(ws.COL_PANEL, (size_t) n * PW * sizeof(uint32_t));
+	int *knew = ws.take<int>(ws.COL_KNEW, 64), *rho = ws.take<int>(ws.COL_RHO, NB * sizeof(int));
+	unsigned int *coop_barrier = ws.take<unsigned int>(ws.COOP_BARRIER, 64);
+	int *coop_cand = ws.take<int>(ws.COOP_CAND, NB * sizeof(int));
+	for (int c0 = 0; c0 < m; c0 += NB) {
+		if (c0 > 0 && (c0 / NB) % 8 == 0) {           // every row already holds a pivot: the rest is reduced
+			int rk = 0;
+			HIP_CHECK(hipMemcpyAsync(&rk, c.rank_d, sizeof(int), hipMemcpyDeviceToHost, stream));
+			HIP_CHECK(hipStreamSynchronize(stream));
+			if (rk >= n)
+				break;
 		}
-		if (next_slot == cache.slots.size())
-			cache.slots.push_back({nullptr, 0});
-		auto &sl = cache.slots[next_slot++];
-		if (sl.second < bytes) {
-			sh::big_free(sl.first);
-			sl.second = bytes + bytes / 4;
-			HIP_CHECK(sh::malloc_or_trim(&sl.first, sl.second));
+		const int width = (m - c0 < NB) ? m - c0 : NB;
+		const PanelArgs g{c.A, c.ld, n, m, c0, width, P, c.flags, c.pivrow, c.pivcol, c.rank_d, knew, rho, c.F};
+		if (n >= c.r.coop_min_rows) {
+			const CoopPanelArgs ca{g, coop_barrier, coop_cand, coop_err};
+			HIP_CHECK(hipMemsetAsync(coop_barrier, 0, sizeof(unsigned int), stream));
+			HIP_CHECK(hipMemsetAsync(coop_cand, 0x7F, NB * sizeof(int), stream));     // 0x7F7F7F7F >= any row index
+			const int G = std::min((n + COOP_THREADS - 1) / COOP_THREADS, 64);
+			hipLaunchKernelGGL(rref_panel_coop_kernel, dim3(G), dim3(COOP_THREADS), 0, stream, ca);
+		} else {
+			hipLaunchKernelGGL(rref_panel_kernel, dim3(1), dim3(PANEL_THREADS), 0, stream, g);
 		}
-		*ptr = sl.first;
-	};
-	auto ws_free = [&](void *ptr) {
-		for (size_t t = 0; t < owned.size(); t++)
-			if (owned[t] == ptr) {
-				sh::big_free(ptr);
-				owned[t] = nullptr;
-				return;
-			}
-	};
-	const Mont M = mont_setup(prime);
-	const MontDev F = to_dev(M);
-	uint32_t *P = nullptr, *B = nullptr;
-	int *flags = nullptr, *pivrow = nullptr, *rank_d = nullptr, *knew = nullptr, *rho = nullptr;
-	const int rmax = (n < m) ? n : m;
-	ws_malloc((void **) &P, (size_t) n * PW * sizeof(uint32_t));
-	ws_malloc((void **) &B, (size_t) NB * (size_t) m * sizeof(uint32_t));
-	ws_malloc((void **) &flags, (size_t) n * sizeof(int));
-	ws_malloc((void **) &pivrow, (size_t) rmax * sizeof(int) + 64);
-	ws_malloc((void **) &rank_d, 64);
-	ws_malloc((void **) &knew, 64);
-	ws_malloc((void **) &rho, NB * sizeof(int));
-	HIP_CHECK(hipMemsetAsync(flags, 0, (size_t) n * sizeof(int), stream));
-	HIP_CHECK(hipMemsetAsync(rank_d, 0, 64, stream));
-	// tall blocks: the panel step is spread over several workgroups (SPASM_HIP_COOP_ROWS rows and up)
-	int coop_min_rows = 2048;
-	if (const char *e = sh::env_get("SPASM_HIP_COOP_ROWS"))
-		coop_min_rows = std::atoi(e);
-	// panel step: tournament (default) or the column-by-column kernels (SPASM_HIP_RREF_PANEL=columns)
-	bool tournament = true;
-	const bool small_prime = prime < 46341;          // 2 p^2 < 2^32: the panel kernels use 24-bit multiplies
-	if (const char *e = sh::env_get("SPASM_HIP_RREF_PANEL"))
-		tournament = std::strcmp(e, "columns") != 0;
-	int *candA = nullptr, *candB = nullptr, *free_count = nullptr, *gamma = nullptr, *cand_first = nullptr, *full_flag = nullptr, *first64 = nullptr, *cand_pivot = nullptr, *live_list = nullptr;
-	uint32_t *Ginv = nullptr, *P4 = nullptr, *Bt4 = nullptr, *Zacc = nullptr;
-	int *rho4 = nullptr, *knew4 = nullptr;
-	signed char *M8 = nullptr, *B8 = nullptr;
+		const int c1 = c0 + width, mr = m - c1;
+		if (mr > 0) {
+			hipLaunchKernelGGL(rref_gather_pivot_rows, dim3(512), dim3(256), 0, stream, c.A, c.ld, c1, mr, rho, knew, c.B);
+			dim3 grid((mr + 63) / 64, (n + 63) / 64);
+			c.timer->before(stream);
+			if (c.r.mfma_ok)
+				hipLaunchKernelGGL(rref_update_mfma, grid, dim3(256), 0, stream, c.A, c.ld, n, c1, mr, P, c.B, knew, c.F);
+			else
+				hipLaunchKernelGGL(rref_update_valu, grid, dim3(256), 0, stream, c.A, c.ld, n, c1, mr, P, c.B, knew, c.F);
+			c.timer->after(stream);
+		}
+		HIP_CHECK(hipGetLastError());
+	}
+}
+
+// Where panel i of the super-panel in hand keeps its things.
+struct PanelSlot {
+	int i, c0, width;
+	uint32_t *P;                       // n x PW, column-major: the panel and its multipliers
+	int *rho, *knew;
+	uint32_t *Ginv;                    // (Ginv, gamma, cand_pivot: two copies, by parity of the panel -- the try of panel i + 1 may run beside the multipliers of panel i)
+	int *gamma, *cand_pivot;
+	signed char *Mh, *Ml;              // its multipliers as digit planes
+};
+
+// The tournament route: super-panels of SPW panels; per panel a try (or the selection tree) and a K = 64 update of the
+// super-panel's own columns, per super-panel one update of everything beyond it.
+struct TournamentRref : RrefCall {
+	static constexpr int OWN_COLS = 2 * MAXSETS * NB + 64;          // columns of the B planes of a panel's own update: the rest of the super-panel and Z
+	RrefStreams *st = nullptr;          // (null: one stream, no lookahead)
+	int *candA{}, *candB{}, *free_count{}, *gamma{}, *cand_first{}, *full_flag{}, *first64{}, *cand_pivot{}, *live_list{}, *rho4{}, *knew4{};
+	uint32_t *Ginv{}, *P4{}, *Bt4{}, *Zacc{}, *alt_tile{};
 	unsigned short *invtab = nullptr;
 	size_t invtab_bytes = 0;
-	if (tournament) {
+	DigitPlanes planes{};
+	int *abort_d{}, *abort_pp{};          // optimistic super-panels: raised by a try that cannot finish its panel; ... word by panel (BlockGjArgs::abort_words)
+	// hand-off words of a lookahead pass (handoff_wait / handoff_signal): by panel, the try is through / workgroups of the lookahead / of the update
+	int *hand_try = nullptr, *hand_look = nullptr, *hand_upd = nullptr;
+	// from super-panel to super-panel
+	bool far_pending = false;          // the far update of the super-panel before may still run on the second stream (ev_far)
+	// a try has failed in this call: from the next super-panel on the zero rows are retired and the candidates of the tries
+	// are spread over the live ones (rref_mark_dead, pick_candidates)
+	bool deficient = false;
+	int optimistic_skip = 0;           // super-panels that are not attempted optimistically
+	int stat_opt_ok = 0, stat_regular = 0, stat_aborts = 0, stat_marked = 0;          // panels done by the optimistic pass / the regular way; super-panels
+	// the super-panel in hand
+	int spi = 0, sp0 = 0, sp_end = 0, npanels = 0;
+	bool have_live = false;            // rows were retired: live_list holds the live_rows others
+	int live_rows = -1;
+	int upd_workgroups[MAXSETS] = {};          // lookahead pass: workgroups of the update of panel i (what look(i + 1) waits for)
+
+	explicit TournamentRref(const RrefCall &c) : RrefCall(c) {}
+	void take_buffers(RrefWorkspace &ws, int64_t prime)
+	{
 		const size_t cand_len = (size_t) std::max(n, ((n + SEL_ROWS - 1) / SEL_ROWS) * NB) + NB;
-		ws_malloc((void **) &candA, cand_len * sizeof(int));
-		ws_malloc((void **) &candB, cand_len * sizeof(int));
-		ws_malloc((void **) &free_count, 64);
-		ws_malloc((void **) &gamma, 2 * NB * sizeof(int));
-		ws_malloc((void **) &cand_first, NB * sizeof(int));
-		ws_malloc((void **) &first64, NB * sizeof(int));
-		ws_malloc((void **) &live_list, (size_t) n * sizeof(int));
-		ws_malloc((void **) &cand_pivot, 2 * NB * sizeof(int));
+		candA = ws.take<int>(ws.CAND_A, cand_len * sizeof(int));
+		candB = ws.take<int>(ws.CAND_B, cand_len * sizeof(int));
+		free_count = ws.take<int>(ws.FREE_COUNT, 64);
+		gamma = ws.take<int>(ws.GAMMA, 2 * NB * sizeof(int));
+		cand_first = ws.take<int>(ws.CAND_FIRST, NB * sizeof(int));
+		first64 = ws.take<int>(ws.FIRST64, NB * sizeof(int));
+		live_list = ws.take<int>(ws.LIVE_LIST, (size_t) n * sizeof(int));
+		cand_pivot = ws.take<int>(ws.CAND_PIVOT, 2 * NB * sizeof(int));
 		HIP_CHECK(hipMemsetAsync(free_count, 0, 64, stream));          // [4]: scan hint of rref_first_free
-		ws_malloc((void **) &P4, (size_t) 2 * MAXSETS * (size_t) n * PW * sizeof(uint32_t));
-		ws_malloc((void **) &Bt4, (size_t) 4 * (size_t) NB * (size_t) m * sizeof(uint32_t));
-		ws_malloc((void **) &rho4, 2 * MAXSETS * NB * sizeof(int));
-		if (small_prime) {
+		P4 = ws.take<uint32_t>(ws.P4, (size_t) 2 * MAXSETS * (size_t) n * PW * sizeof(uint32_t));
+		Bt4 = ws.take<uint32_t>(ws.BT4, (size_t) 4 * (size_t) NB * (size_t) m * sizeof(uint32_t));
+		rho4 = ws.take<int>(ws.RHO4, 2 * MAXSETS * NB * sizeof(int));
+		if (r.small_prime) {
 			invtab_bytes = ((size_t) prime * 2 + 15) / 16 * 16;
-			ws_malloc((void **) &invtab, invtab_bytes + 64);
+			invtab = ws.take<unsigned short>(ws.INVTAB, invtab_bytes + 64);
 			hipLaunchKernelGGL(rref_inverse_table, dim3(((unsigned) prime + 255) / 256), dim3(256), 0, stream, invtab, F);
 			static bool configured = false;
 			if (!configured) {
-				HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&rref_block_gj<true, 8>),
-				                              hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-				HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&rref_try_inverse),
-				                              hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+				HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&rref_block_gj<true, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+				HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&rref_try_inverse), hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
 				configured = true;
 			}
 		}
@@ -2157,688 +2368,489 @@ int device_rref(int64_t prime, int n, int m, uint32_t *dA, int64_t ld, int *d_pi
 		// (M planes: one per panel of two super-panels -- the far update of the previous one may still read its own -- and
 		//  as many again for the accumulated multipliers Z; B planes: one per set, one more for a panel's own update, which
 		//  covers the rest of the super-panel and the Z columns)
-		ws_malloc((void **) &M8, (size_t) 4 * MAXSETS * 2 * (size_t) n * 64);
-		ws_malloc((void **) &B8, (size_t) MAXSETS * 2 * (size_t) m * 64 + (size_t) 2 * (2 * MAXSETS * NB + 64) * 64);
-		ws_malloc((void **) &Zacc, (size_t) n * (size_t) (MAXSETS * NB) * sizeof(uint32_t));
-		ws_malloc((void **) &knew4, 2 * MAXSETS * 16 * sizeof(int));
-		ws_malloc((void **) &full_flag, 256);
+		planes = DigitPlanes{ws.take<signed char>(ws.M8, (size_t) 4 * MAXSETS * 2 * (size_t) n * 64),
+		                     ws.take<signed char>(ws.B8, (size_t) MAXSETS * 2 * (size_t) m * 64 + (size_t) 2 * OWN_COLS * 64), (size_t) n, (size_t) m};
+		Zacc = ws.take<uint32_t>(ws.ZACC, (size_t) n * (size_t) (MAXSETS * NB) * sizeof(uint32_t));
+		knew4 = ws.take<int>(ws.KNEW4, 2 * MAXSETS * 16 * sizeof(int));
+		full_flag = ws.take<int>(ws.FULL_FLAG, 256);
 		HIP_CHECK(hipMemsetAsync(full_flag, 0, 256, stream));          // [0] full, [4] gj_done, [8] try_state, [12] abort, [16 .. 16 + MAXSETS) abort by panel
-		ws_malloc((void **) &Ginv, 2 * NB * NB * sizeof(uint32_t));
+		abort_d = full_flag + 12;
+		abort_pp = full_flag + 16;
+		Ginv = ws.take<uint32_t>(ws.GINV, 2 * NB * NB * sizeof(uint32_t));
 	}
-	unsigned int *coop_barrier = nullptr;
-	int *coop_cand = nullptr, *coop_err = nullptr;
-	ws_malloc((void **) &coop_barrier, 64);
-	ws_malloc((void **) &coop_cand, NB * sizeof(int));
-	ws_malloc((void **) &coop_err, 64);
-	HIP_CHECK(hipMemsetAsync(coop_err, 0, 64, stream));
-	hipEvent_t e0 = nullptr, e1 = nullptr;
-	if (ms_update != nullptr) {
-		HIP_CHECK(hipEventCreate(&e0));
-		HIP_CHECK(hipEventCreate(&e1));
+
+	// (after rref_streams, when the call runs its tries one panel ahead)
+	void take_lookahead_buffers(RrefWorkspace &ws)
+	{
+		alt_tile = ws.take<uint32_t>(ws.ALT_TILE, (size_t) 2 * NB * NB * sizeof(uint32_t) + 3 * MAXSETS * sizeof(int));          // (two tiles, by parity of the panel; then the hand-off words)
+		hand_try = reinterpret_cast<int *>(alt_tile + (size_t) 2 * NB * NB);
+		hand_look = hand_try + MAXSETS, hand_upd = hand_try + 2 * MAXSETS;
 	}
-	float total_update = 0.f;
-	const bool mfma_ok = use_mfma && prime <= 65279;      // two signed base-256 digits must fit int8
-	hipStream_t stream2 = nullptr;
-	hipEvent_t ev_near = nullptr, ev_far = nullptr;
-	const bool two_streams = tournament && mfma_ok && !sh::env_get("SPASM_HIP_RREF_ONE_STREAM");
-	if (two_streams) {
-		HIP_CHECK(hipEventCreate(&ev_near));
-		HIP_CHECK(hipEventCreate(&ev_far));
+
+	static constexpr int64_t ldz = (int64_t) MAXSETS * NB;
+	signed char *Bown_h() const { return planes.Bh(MAXSETS); }
+	signed char *Bown_l() const { return Bown_h() + (size_t) OWN_COLS * 64; }
+
+	// (sets alternate between two halves by super-panel: the far update of the previous super-panel may
+	//  still be reading its multipliers on the second stream)
+	PanelSlot panel(int i) const
+	{
+		const int slot = (spi & 1) * MAXSETS + i, par = i & 1, c0 = sp0 + i * NB;
+		return PanelSlot{i, c0, std::min(NB, m - c0), P4 + (size_t) slot * (size_t) n * PW, rho4 + slot * NB, knew4 + slot * 16,
+		                 Ginv + (size_t) par * NB * NB, gamma + par * NB, cand_pivot + par * NB, planes.Mh(slot), planes.Ml(slot)};
 	}
-	// one panel ahead (rref_lookahead): the tries of an optimistic super-panel on a stream of their own, beside the multipliers and
-	// updates of the panel before.  Streams and events are kept between calls (per host thread).
-	struct Ahead {
-		int dev = -1;
-		hipStream_t s_try = nullptr, s_far = nullptr;
-		hipEvent_t ev_try[MAXSETS] = {}, ev_upd[MAXSETS] = {}, ev_look[MAXSETS] = {}, ev_start = nullptr;
-	};
-	static thread_local Ahead ahead;
-	bool use_ahead = tournament && mfma_ok && prime < 65536 && (sh::env_get("SPASM_HIP_RREF_LOOKAHEAD") == nullptr || std::atoi(sh::env_get("SPASM_HIP_RREF_LOOKAHEAD")) != 0);
-	uint32_t *alt_tile = nullptr;
-	if (use_ahead || two_streams) {
-		int dev = 0;
-		HIP_CHECK(hipGetDevice(&dev));
-		if (ahead.dev != dev) {
-			// (Tried: disjoint compute units for the two streams (hipExtStreamCreateWithCUMask: sixteen for the tries, the rest for the far
-			//  updates) -- the trace shows a try at 75-79 us instead of 44 whenever the far update of the super-panel before shares its
-			//  compute unit.  The call went from 8.3 to 16 ms: masked queues are served far more slowly on this stack.  Plain streams.)
-			HIP_CHECK(hipStreamCreateWithFlags(&ahead.s_far, hipStreamNonBlocking));
-			HIP_CHECK(hipStreamCreateWithFlags(&ahead.s_try, hipStreamNonBlocking));
-			for (int t = 0; t < MAXSETS; t++) {
-				HIP_CHECK(hipEventCreateWithFlags(&ahead.ev_try[t], hipEventDisableTiming));
-				HIP_CHECK(hipEventCreateWithFlags(&ahead.ev_upd[t], hipEventDisableTiming));
-				HIP_CHECK(hipEventCreateWithFlags(&ahead.ev_look[t], hipEventDisableTiming));
+
+	// (a block on which tries fail -- dependent columns, or rows that depend on each other --: the try that takes what its
+	//  candidates give, with the proof in the multiplier kernel; see BlockGjArgs)
+	bool takes_what_comes(const PanelSlot &p, bool optimistic) const { return optimistic && have_live && r.small_prime && r.small16 && r.mfma_ok && p.width == NB; }
+
+	// ---- the steps of a panel ----
+	// The arguments of the Gauss-Jordan kernels of panel p.  abort_c: the abort word an optimistic panel looks at (null: a regular
+	// panel), by_panel: ... one of a word per panel (passes with the tries one panel ahead), done_word: counted up when the try is
+	// through, with_alt: the try reads the tile rref_lookahead left instead of A.  In the order of the struct: the panel and its
+	// outputs | try mode | abort words | the first free rows (an optimistic try finds them itself unless rref_lookahead did) | the rest.
+	BlockGjArgs fill_block_gj(const PanelSlot &p, const int *abort_c, bool by_panel, int *done_word, bool with_alt) const
+	{
+		return BlockGjArgs{A, ld, n, p.c0, p.width, /* cand */ nullptr, cand_first, full_flag, invtab, p.Ginv, p.gamma, flags, pivrow, pivcol, rank_d, p.knew, p.rho, p.cand_pivot,
+		                   /* mode */ 1, first64, free_count + 2, /* gj_done */ full_flag + 4, /* try_state */ full_flag + 8, p.c0 / NB,
+		                   const_cast<int *>(abort_c), p.i, by_panel ? abort_pp : nullptr, abort_d, MAXSETS,
+		                   (abort_c != nullptr && !with_alt) ? flags : nullptr, free_count + 4, first64, free_count + 2,
+		                   have_live ? live_list : nullptr, free_count + 10, done_word, with_alt ? alt_tile + (size_t) (p.i & 1) * NB * NB : nullptr, F};
+	}
+
+	// Gauss-Jordan straight on the first 64 free rows (try mode): when they give a pivot in every column of the
+	// panel (the usual case while the block is not exhausted) everything up to the regular call returns at once
+	void enqueue_try(hipStream_t s, const PanelSlot &p, BlockGjArgs bg) const
+	{
+		bg.mode = takes_what_comes(p, bg.abort != nullptr) ? 2 : 1;
+		if (bg.mode == 1 && r.fast_try)
+			hipLaunchKernelGGL(rref_try_inverse, dim3(1), dim3(256), invtab_bytes, s, bg);
+		else
+			hipLaunchKernelGGL((r.small_prime ? rref_block_gj<true, 8> : rref_block_gj<false, 8>), dim3(1), dim3(1024), invtab_bytes, s, bg);          // (no table: 0 bytes)
+	}
+
+	// The regular route to the pivots of a panel: the first 64 free rows alone, by selection (when the try was skipped or failed),
+	// then the tournament over all free rows and the Gauss-Jordan of its 64 winners.  straight: no look at the first free rows.
+	void enqueue_selection(hipStream_t s, const PanelSlot &p, BlockGjArgs bg, bool straight) const
+	{
+		if (!straight)
+			hipLaunchKernelGGL(r.small_prime ? rref_select_first<true> : rref_select_first<false>, dim3(1), dim3(256), 0, s, A, ld, p.c0, p.width, first64, free_count + 2, cand_first,
+			                   F, full_flag, full_flag + 4);
+		// (everything from here to the Gauss-Jordan block returns at once when that was enough)
+		hipLaunchKernelGGL(rref_free_list, dim3(1), dim3(1024), 0, s, flags, n, candA, free_count, full_flag, straight ? full_flag : nullptr);
+		int n_in = have_live ? std::max(live_rows, 1) : n;          // (the free rows are among the live ones: fewer levels on a block that is running out)
+		const int *count_dev = free_count;
+		int *src = candA, *dst = candB;
+		for (;;) {
+			const int wgs = (n_in + SEL_ROWS - 1) / SEL_ROWS;
+			hipLaunchKernelGGL(r.small_prime ? rref_select_kernel<true> : rref_select_kernel<false>, dim3(wgs), dim3(SEL_ROWS), 0, s, A, ld, p.c0, p.width, src, n_in, count_dev, dst,
+			                   F, full_flag, nullptr);
+			// (the first level reads candA and writes candB; candA is then free)
+			std::swap(src, dst);
+			n_in = wgs * NB;
+			count_dev = nullptr;
+			if (wgs == 1)
+				break;
+		}
+		bg.cand = src;
+		bg.mode = 0;
+		hipLaunchKernelGGL((r.small_prime ? rref_block_gj<true, 8> : rref_block_gj<false, 8>), dim3(1), dim3(1024), invtab_bytes, s, bg);          // (no table: 0 bytes)
+	}
+
+	// The multipliers of panel p and its pivot rows, then the K = 64 update of the columns of the super-panel, from this panel
+	// on, and (matrix cores) of the multipliers of its earlier panels, blocks 0 .. i - 1 of Z.  abort_c: as fill_block_gj.
+	// ahead: the try ran on its own stream -- the multipliers wait for its hand-off word and the update counts its workgroups
+	// up for the lookahead of the next panel; look_follows: ... and the update waits for the lookahead of this one.
+	void enqueue_multipliers_and_update(hipStream_t s, const PanelSlot &p, const int *abort_c, bool ahead = false, bool look_follows = false)
+	{
+		const int c0 = p.c0, i = p.i;
+		MultArgs ma{A, ld, n, m, c0, p.Ginv, p.gamma, p.knew, p.P, F, p.rho, p.cand_pivot, r.mfma_ok ? p.Mh : nullptr, r.mfma_ok ? p.Ml : nullptr,
+		            r.mfma_ok ? Zacc + (size_t) i * NB : nullptr /* M_s becomes block `i` of Z */, ldz, abort_c,
+		            takes_what_comes(p, abort_c != nullptr) ? flags : nullptr, abort_d, i, ahead ? hand_try + i : nullptr,
+		            (ahead && look_follows) ? hand_look + i : nullptr, LOOK_WGS};
+		const int nmult = (n + 63) / 64, mr_sp = sp_end - c0;
+		UpdSets one{};
+		one.P[0] = p.P;
+		one.B[0] = B;
+		one.knew[0] = p.knew;
+		one.nsets = 1;
+		one.abort = abort_c;
+		int tiles = (mr_sp + 63) / 64;
+		if (r.mfma_ok) {
+			// multipliers and the digit planes of the pivot rows in one launch
+			const int tiles1 = (mr_sp + 63) / 64, mr2 = i * NB;
+			GatherArgs ga{A, ld, c0, mr_sp, p.rho, p.knew, Bown_h(), Bown_l(), nullptr, F, Zacc, ldz, tiles1, mr2, abort_c};
+			const int ngather = (tiles1 * 64 + mr2 + 255) / 256;
+			hipLaunchKernelGGL(r.small16 ? rref_mult_gather<true> : rref_mult_gather<false>, dim3(nmult + ngather), dim3(256), 0, s, ma, ga, nmult);
+			one.Mh[0] = p.Mh;
+			one.Ml[0] = p.Ml;
+			one.Bh[0] = Bown_h();
+			one.Bl[0] = Bown_l();
+			if (mr2 > 0) {
+				one.Z2 = Zacc;
+				one.ld2 = ldz;
+				one.tiles1 = tiles1;
+				one.mr2 = mr2;
+				tiles = tiles1 + mr2 / 64;
 			}
-			HIP_CHECK(hipEventCreateWithFlags(&ahead.ev_start, hipEventDisableTiming));
-			ahead.dev = dev;
+		} else {
+			hipLaunchKernelGGL(r.small16 ? rref_multipliers<true> : rref_multipliers<false>, dim3(nmult), dim3(256), 0, s, ma);
+			hipLaunchKernelGGL(rref_gather_pivot_rows, dim3(512), dim3(256), 0, s, A, ld, c0, mr_sp, p.rho, p.knew, B);
 		}
-		if (use_ahead) {
-			// the hand-offs need a kernel of each stream on the device at the same time: asked once per pair of streams (handoff_probe)
-			struct Probed {
-				hipStream_t main = nullptr, tries = nullptr;
-				bool met = false, asked = false;
-			};
-			static thread_local Probed probed;
-			if (!probed.asked || probed.main != stream || probed.tries != ahead.s_try) {
-				int *pw = nullptr, met[2] = {0, 0};
-				ws_malloc((void **) &pw, 4 * sizeof(int));
-				HIP_CHECK(hipMemsetAsync(pw, 0, 4 * sizeof(int), stream));
-				HIP_CHECK(hipEventRecord(ahead.ev_start, stream));
-				HIP_CHECK(hipStreamWaitEvent(ahead.s_try, ahead.ev_start, 0));
-				hipLaunchKernelGGL(handoff_probe, dim3(1), dim3(1), 0, stream, pw, 0, pw + 2);
-				hipLaunchKernelGGL(handoff_probe, dim3(1), dim3(1), 0, ahead.s_try, pw, 1, pw + 2);
-				HIP_CHECK(hipEventRecord(ahead.ev_look[0], ahead.s_try));
-				HIP_CHECK(hipStreamWaitEvent(stream, ahead.ev_look[0], 0));
-				HIP_CHECK(hipMemcpyAsync(met, pw + 2, sizeof(met), hipMemcpyDeviceToHost, stream));
-				HIP_CHECK(hipStreamSynchronize(stream));
-				ws_free(pw);
-				probed.main = stream;
-				probed.tries = ahead.s_try;
-				probed.met = met[0] != 0 && met[1] != 0;
-				probed.asked = true;
-				if (!probed.met && sh::verbose() >= 1)
-					fprintf(stderr, "[spasm_hip] dense RREF: kernels of two streams do not run side by side here (a tool that serialises launches?): no lookahead\n");
-			}
-			use_ahead = probed.met;
+		if (ahead) {
+			one.done_word = hand_upd + i;
+			upd_workgroups[i] = tiles * ((n + 63) / 64);
 		}
-		if (use_ahead)
-			ws_malloc((void **) &alt_tile, (size_t) 2 * NB * NB * sizeof(uint32_t) + 3 * MAXSETS * sizeof(int));          // (two tiles, by parity of the panel; then the hand-off words)
-		if (two_streams)
-			stream2 = ahead.s_far;
+		const dim3 grid(tiles, (n + 63) / 64);
+		timer->before(s);
+		if (r.mfma_ok)
+			hipLaunchKernelGGL(rref_update_mfma_multi, grid, dim3(256), 0, s, A, ld, n, c0, mr_sp, one, F);
+		else
+			hipLaunchKernelGGL(rref_update_valu, grid, dim3(256), 0, s, A, ld, n, c0, mr_sp, p.P, B, p.knew, F);
+		timer->after(s);
+		HIP_CHECK(hipGetLastError());
 	}
-	auto timed = [&](auto &&launch) {
-		if (ms_update != nullptr)
-			HIP_CHECK(hipEventRecord(e0, stream));
-		launch();
-		if (ms_update != nullptr) {
-			HIP_CHECK(hipEventRecord(e1, stream));
-			HIP_CHECK(hipEventSynchronize(e1));
-			float ms;
-			HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-			total_update += ms;
+
+	// ---- the three ways through a panel ----
+	// Optimistic: first-free rows and try in one kernel, multipliers, update -- none of the selection kernels (they return at
+	// once when the try succeeds, but a launch is a launch: 30 us per panel).
+	void optimistic_panel(int i)
+	{
+		const PanelSlot p = panel(i);
+		enqueue_try(stream, p, fill_block_gj(p, abort_d, false, nullptr, false));
+		enqueue_multipliers_and_update(stream, p, abort_d);
+	}
+
+	// Regular: first free rows, try, selection (at once when the try was enough), multipliers, update.
+	// (a block on which the tries fail, rows retired: straight to the tournament, three launches fewer)
+	void regular_panel(int i)
+	{
+		const PanelSlot p = panel(i);
+		const BlockGjArgs bg = fill_block_gj(p, nullptr, false, nullptr, false);
+		const bool straight = have_live;
+		if (!straight) {
+			hipLaunchKernelGGL(rref_first_free, dim3(1), dim3(64), 0, stream, flags, n, free_count + 4, first64, free_count + 2, (const int *) nullptr, free_count + 10);
+			enqueue_try(stream, p, bg);
 		}
-	};
-	if (sh::env_get("SPASM_HIP_RREF_TIMING")) {
+		enqueue_selection(stream, p, bg, straight);
+		enqueue_multipliers_and_update(stream, p, nullptr);
+	}
+
+	// One panel ahead, panels start .. npanels - 1 (plain optimistic passes only: full panels, no list of live rows, p < 2^16).
+	// The try stream: try(start), look(start), try(start + 1), ... back to back, no event between them.  The main
+	// stream: multipliers(i) (its workgroups wait for try(i)'s word), update(i) (waits for look(i): it REWRITES the
+	// next panel's columns of the candidates and of the pivot rows, which look(i) reads), ...  look(i) waits for
+	// the workgroups of update(i - 1).  No cycle: every wait is for a kernel that is earlier in BOTH orders.
+	void lookahead_pass(int start)
+	{
+		HIP_CHECK(hipMemsetAsync(abort_pp, 0, MAXSETS * sizeof(int), stream));
+		HIP_CHECK(hipMemsetAsync(hand_try, 0, 3 * MAXSETS * sizeof(int), stream));
+		HIP_CHECK(hipEventRecord(st->ev_start, stream));
+		HIP_CHECK(hipStreamWaitEvent(st->s_try, st->ev_start, 0));
+		for (int i = start; i < npanels; i++) {
+			const PanelSlot p = panel(i);
+			// try(i): from A for the first panel of the pass, from look(i - 1)'s tile after that
+			enqueue_try(st->s_try, p, fill_block_gj(p, abort_pp + i, true, hand_try + i, i > start));
+			const bool next_full = i + 1 < npanels && p.c0 + 2 * NB <= m;
+			if (next_full) {
+				LookArgs la{A, ld, n, p.c0, p.Ginv, p.rho, p.knew, flags, free_count + 4, first64, free_count + 2,
+				            alt_tile + (size_t) ((i + 1) & 1) * NB * NB, abort_pp + i, (i > start) ? hand_upd + (i - 1) : nullptr, (i > start) ? upd_workgroups[i - 1] : 0,
+				            hand_look + i, F};
+				hipLaunchKernelGGL(rref_lookahead, dim3(LOOK_WGS), dim3(256), 0, st->s_try, la);
+			}
+			enqueue_multipliers_and_update(stream, p, abort_pp + i, true, next_full);
+			if (!next_full && i + 1 < npanels) {
+				// (a narrow last panel: its try reads A itself, after update(i))
+				HIP_CHECK(hipEventRecord(st->ev_upd[i], stream));
+				HIP_CHECK(hipStreamWaitEvent(st->s_try, st->ev_upd[i], 0));
+			}
+		}
+	}
+
+	// ---- the steps of a super-panel ----
+	// Done when every row holds a pivot, or when the rows that do not are zero from here on (a block of
+	// low rank: most of its panels would find nothing).  First on the columns of this super-panel, which the far
+	// update of the previous one -- still running on the second stream -- does not write: a free row that is not
+	// zero there settles the question, and the panels start beside that update (the trace of round 6 showed the
+	// chain idle for the whole of it, 0.55 ms, at each of these checks); only when they are all zero there is the
+	// update waited for and the rest looked at.
+	bool finished()
+	{
+		int rk_nz[2] = {0, 0};
+		const bool split = far_pending && sp_end < m;          // (no update in flight: one look at everything)
+		for (int pass = 0; pass < 2; pass++) {
+			const bool rest = pass == 1;
+			if (rest)
+				HIP_CHECK(hipStreamWaitEvent(stream, st->ev_far, 0));
+			HIP_CHECK(hipMemsetAsync(free_count + 8, 0, sizeof(int), stream));
+			hipLaunchKernelGGL(rref_free_nonzero, dim3(512), dim3(256), 0, stream, A, ld, n, (split && !rest) ? sp_end : m, rest ? sp_end : sp0, flags, free_count + 8);
+			HIP_CHECK(hipMemcpyAsync(&rk_nz[0], rank_d, sizeof(int), hipMemcpyDeviceToHost, stream));
+			HIP_CHECK(hipMemcpyAsync(&rk_nz[1], free_count + 8, sizeof(int), hipMemcpyDeviceToHost, stream));
+			HIP_CHECK(hipStreamSynchronize(stream));
+			if (rk_nz[0] >= n || rk_nz[1] != 0 || !split)
+				break;
+		}
+		return rk_nz[0] >= n || rk_nz[1] == 0;
+	}
+
+	// The rows that are zero from sp0 on are retired: live_list, live_rows.
+	// (reads the columns from sp0 on: the far update of the previous super-panel must have landed -- the overlap of that
+	//  update with the panel steps is given up here, on blocks whose panel steps are the slow part anyway)
+	void retire()
+	{
+		if (far_pending)
+			HIP_CHECK(hipStreamWaitEvent(stream, st->ev_far, 0));
+		HIP_CHECK(hipMemsetAsync(free_count + 10, 0, sizeof(int), stream));
+		hipLaunchKernelGGL(rref_mark_dead, dim3(512), dim3(256), 0, stream, A, ld, n, m, sp0, flags, live_list, free_count + 10);
+		HIP_CHECK(hipMemcpyAsync(&live_rows, free_count + 10, sizeof(int), hipMemcpyDeviceToHost, stream));
 		HIP_CHECK(hipStreamSynchronize(stream));
-		fprintf(stderr, "[rref timing] allocations + setup: %.3f ms\n", 1e3 * (wtime() - t_entry));
+		have_live = true;
 	}
-	int stat_opt_ok = 0, stat_regular = 0, stat_aborts = 0, stat_marked = 0;          // panels done by the optimistic pass / the regular way; super-panels
-	if (tournament) {
-		const bool small16 = prime < 65536;
-		const bool try_first = true;
-		// the 64 x 64 inversion kernel for the try: signed representatives with deferred reduction need 4 B^2 + B < 2^31, B = p/2 + p/64 + 1
-		bool fast_try = small_prime && (4 * (prime / 2 + prime / 64 + 1) * (prime / 2 + prime / 64 + 1) + (prime / 2 + prime / 64 + 1) <= 0x7FFFFFFFll);
-		// panels per super-panel: eight on the matrix cores (K = 512 per pass over the matrix), four with VALU updates
-		const int SPW = mfma_ok ? MAXSETS : 4;
-		const int64_t ldz = (int64_t) MAXSETS * NB;
-		signed char *Bown_h = B8 + (size_t) MAXSETS * 2 * (size_t) m * 64, *Bown_l = Bown_h + (size_t) (2 * MAXSETS * NB + 64) * 64;
-		bool far_pending = false;
-		const bool optimistic_enabled = true;
-		bool optimistic_ok = optimistic_enabled;
-		int optimistic_skip = 0;
-		// a try has failed in this call: from the next super-panel on the zero rows are retired and the candidates of the tries
-		// are spread over the live ones (rref_mark_dead, pick_candidates)
-		bool deficient = false;
-		const bool retire_rows = true;
-		uint32_t *set_P[MAXSETS] = {};
-		int *set_rho[MAXSETS] = {}, *set_knew[MAXSETS] = {};
-		signed char *set_Mh[MAXSETS] = {}, *set_Ml[MAXSETS] = {};
-		for (int sp0 = 0, spi = 0; sp0 < m; sp0 += SPW * NB, spi++) {
-			if (spi == 1 || spi == 2 || (spi > 0 && spi % 4 == 0)) {
-				// done when every row holds a pivot, or when the rows that do not are zero from here on (a block of
-				// low rank: most of its panels would find nothing).  First on the columns of this super-panel, which the far
-				// update of the previous one -- still running on the second stream -- does not write: a free row that is not
-				// zero there settles the question, and the panels start beside that update (the trace of round 6 showed the
-				// chain idle for the whole of it, 0.55 ms, at each of these checks); only when they are all zero there is the
-				// update waited for and the rest looked at.
-				int rk_nz[2] = {0, 0};
-				const int own_end = std::min(m, sp0 + SPW * NB);
-				const bool split = far_pending && own_end < m;          // (no update in flight: one look at everything)
-				for (int pass = 0; pass < 2; pass++) {
-					const bool rest = pass == 1;
-					if (rest)
-						HIP_CHECK(hipStreamWaitEvent(stream, ev_far, 0));
-					HIP_CHECK(hipMemsetAsync(free_count + 8, 0, sizeof(int), stream));
-					hipLaunchKernelGGL(rref_free_nonzero, dim3(512), dim3(256), 0, stream, dA, ld, n, (split && !rest) ? own_end : m, rest ? own_end : sp0, flags, free_count + 8);
-					HIP_CHECK(hipMemcpyAsync(&rk_nz[0], rank_d, sizeof(int), hipMemcpyDeviceToHost, stream));
-					HIP_CHECK(hipMemcpyAsync(&rk_nz[1], free_count + 8, sizeof(int), hipMemcpyDeviceToHost, stream));
-					HIP_CHECK(hipStreamSynchronize(stream));
-					if (rk_nz[0] >= n || rk_nz[1] != 0 || !split)
-						break;
-				}
-				if (rk_nz[0] >= n || rk_nz[1] == 0)
-					break;
+
+	// Passes of optimistic panel steps; a pass ends at the panel whose try (or proof) failed: the host looks at the flag once per
+	// pass.  The first failure of a call switches to the tries that take what comes (rows retired, candidates spread:
+	// BlockGjArgs mode 2) and the pass is taken up again at that panel; a failure in that mode sends the one panel the regular
+	// way, and after three of them the rest of the super-panel goes that way.  Returns the first panel that is left to do.
+	int optimistic_passes()
+	{
+		int start = 0, fallbacks = 0;
+		while (start < npanels) {
+			HIP_CHECK(hipMemsetAsync(abort_d, 0, sizeof(int), stream));
+			// (knew[1] of a slot = the pivots a mode-2 try has taken, for rref_rollback: nothing yet)
+			HIP_CHECK(hipMemset2DAsync(knew4 + (size_t) (spi & 1) * MAXSETS * 16 + 1, 16 * sizeof(int), 0, sizeof(int), MAXSETS, stream));
+			if (r.use_ahead && !have_live && r.small16 && npanels - start >= 2 && n <= r.look_rows) {
+				lookahead_pass(start);
+			} else {
+				for (int i = start; i < npanels; i++)
+					optimistic_panel(i);
 			}
-			bool have_live = false;
-			int live_rows = -1;
-			auto retire = [&]() {
-				// (reads the columns from sp0 on: the far update of the previous super-panel must have landed -- the overlap of that
-				//  update with the panel steps is given up here, on blocks whose panel steps are the slow part anyway)
-				if (far_pending)
-					HIP_CHECK(hipStreamWaitEvent(stream, ev_far, 0));
-				HIP_CHECK(hipMemsetAsync(free_count + 10, 0, sizeof(int), stream));
-				hipLaunchKernelGGL(rref_mark_dead, dim3(512), dim3(256), 0, stream, dA, ld, n, m, sp0, flags, live_list, free_count + 10);
-				HIP_CHECK(hipMemcpyAsync(&live_rows, free_count + 10, sizeof(int), hipMemcpyDeviceToHost, stream));
-				HIP_CHECK(hipStreamSynchronize(stream));
-				have_live = true;
-			};
-			if (deficient && retire_rows) {
+			int raised = 0;
+			HIP_CHECK(hipMemcpyAsync(&raised, abort_d, sizeof(int), hipMemcpyDeviceToHost, stream));
+			HIP_CHECK(hipStreamSynchronize(stream));
+			const int stop = raised != 0 ? raised - 1 : npanels;
+			stat_opt_ok += stop - start;
+			start = stop;
+			if (raised == 0)
+				break;
+			stat_aborts += 1;
+			if (have_live) {
+				// (a mode-2 try whose proof failed has taken its pivots already: they go back before the panel is redone)
+				const PanelSlot p = panel(stop);
+				if (r.timing) {
+					int took = 0, tc = 0;
+					HIP_CHECK(hipMemcpy(&took, p.knew + 1, sizeof(int), hipMemcpyDeviceToHost));
+					HIP_CHECK(hipMemcpy(&tc, free_count + 2, sizeof(int), hipMemcpyDeviceToHost));
+					fprintf(stderr, "[rref timing] super-panel %d: the try of panel %d took %d pivots from %d candidates (%d live rows) and the proof failed\n", spi, stop, took, tc,
+					        live_rows);
+				}
+				hipLaunchKernelGGL(rref_rollback, dim3(1), dim3(64), 0, stream, p.rho, p.knew, flags, rank_d);
+				regular_panel(stop);
+				stat_regular += 1;
+				start = stop + 1;
+				fallbacks += 1;
+				if (fallbacks >= 3)
+					break;
+			} else {
+				deficient = true;          // (fast_try, which these passes require, says p < 46341: the retired rows' kernels apply)
+				retire();
+			}
+		}
+		return start;
+	}
+
+	// Everything beyond the super-panel, K = 64 npanels in one pass: the near part (the next super-panel's own columns) on
+	// this stream, the far part on the second one.
+	void far_update()
+	{
+		const int nsets = npanels, mrT = m - sp_end;
+		// What is read here -- the rows rho_i beyond the super-panel -- is written by the far
+		// update of the previous super-panel on the second stream: wait for it here, not earlier -- the panel steps
+		// (latency-bound, one workgroup most of the time) ran beside it.
+		if (far_pending)
+			HIP_CHECK(hipStreamWaitEvent(stream, st->ev_far, 0));
+		UpdSets S{};
+		if (r.mfma_ok) {
+			// C += sum_i M'_i C[rho_i]: M'_i = block i of Z (digit planes), C[rho_i] = the rows as they stand
+			const int zset = 2 * MAXSETS + (spi & 1) * MAXSETS;
+			hipLaunchKernelGGL(rref_split_Z, dim3((n + 63) / 64, nsets), dim3(256), 0, stream, Zacc, ldz, n, nsets, planes.Mh(zset), (int64_t) 2 * n * 64, F);
+			GatherSets gs{};
+			for (int s = 0; s < nsets; s++) {
+				const PanelSlot p = panel(s);
+				gs.rho[s] = p.rho;
+				gs.knew[s] = p.knew;
+				gs.Bh[s] = planes.Bh(s);
+				gs.Bl[s] = planes.Bl(s);
+				S.knew[s] = p.knew;
+				S.Mh[s] = planes.Mh(zset + s);
+				S.Ml[s] = planes.Ml(zset + s);
+				S.Bh[s] = planes.Bh(s);
+				S.Bl[s] = planes.Bl(s);
+			}
+			hipLaunchKernelGGL(rref_gather_split_sets, dim3((mrT + 255) / 256, nsets), dim3(256), 0, stream, A, ld, sp_end, mrT, gs, F);
+		} else {
+			for (int s = 0; s < nsets; s++) {
+				const PanelSlot p = panel(s);
+				S.nsets = s;          // the sets before this one
+				uint32_t *Bt_s = Bt4 + (size_t) s * (size_t) NB * (size_t) m;
+				hipLaunchKernelGGL(r.small16 ? rref_trailing_B<true> : rref_trailing_B<false>, dim3((mrT + 255) / 256, NB), dim3(256), 0, stream, A, ld, n, sp_end, mrT, S, p.rho, p.knew,
+				                   Bt_s, F);
+				S.P[s] = p.P;
+				S.B[s] = Bt_s;
+				S.knew[s] = p.knew;
+			}
+		}
+		S.nsets = nsets;
+		const int near = r.two_streams ? std::min(mrT, r.SPW * NB) : mrT;
+		// (a 64 x 128 tile kernel, two waves per SIMD, 256 registers, was built in round 5 and took 24 % less serialised time for the
+		//  updates -- and 5 % MORE for the call, with and without the lookahead of round 6: removed.  Round 6 also built a 128 x 128
+		//  tile kernel for the far part -- 64 x 64 per wave, three accumulators per 32 x 32 tile, half the LDS bytes per matrix
+		//  instruction, operands read one phase ahead, two LDS buffers, ONE workgroup per CU (320 registers): bit-identical and no
+		//  faster, 5.08 against 5.00 ms serialised.  With K = 512 a workgroup is prologue (its 64 KB of C, the first planes),
+		//  eight short sets whose planes arrive later than the 0.43 us the set before takes to multiply, and an epilogue; with one
+		//  workgroup per CU these phases have nothing to hide behind.  What the far update needs is several workgroups per CU in
+		//  different phases, which is what the 64 x 64 kernel has: NOTES/round6.md.)
+		const dim3 grid((near + 63) / 64, (n + 63) / 64);
+		timer->before(stream);
+		if (r.mfma_ok) {
+			hipLaunchKernelGGL(rref_update_mfma_multi, grid, dim3(256), 0, stream, A, ld, n, sp_end, near, S, F);
+		} else {
+			for (int s = 0; s < nsets; s++)
+				hipLaunchKernelGGL(rref_update_valu, grid, dim3(256), 0, stream, A, ld, n, sp_end, mrT, S.P[s], S.B[s], S.knew[s], F);
+		}
+		timer->after(stream);
+		far_pending = false;
+		if (near < mrT) {
+			UpdSets Sf = S;
+			for (int s = 0; s < nsets; s++) {
+				Sf.Bh[s] = S.Bh[s] + (size_t) near * 64;
+				Sf.Bl[s] = S.Bl[s] + (size_t) near * 64;
+			}
+			HIP_CHECK(hipEventRecord(st->ev_near, stream));
+			HIP_CHECK(hipStreamWaitEvent(st->s_far, st->ev_near, 0));
+			const dim3 grid_far((mrT - near + 63) / 64, (n + 63) / 64);
+			timer->before(st->s_far);
+			hipLaunchKernelGGL(rref_update_mfma_multi, grid_far, dim3(256), 0, st->s_far, A, ld, n, sp_end + near, mrT - near, Sf, F);
+			HIP_CHECK(hipEventRecord(st->ev_far, st->s_far));
+			far_pending = true;
+			timer->after(st->s_far, st->ev_far);          // (timing runs serialise the two streams)
+		}
+		HIP_CHECK(hipGetLastError());
+	}
+
+	void run()
+	{
+		for (spi = 0, sp0 = 0; sp0 < m; sp0 += r.SPW * NB, spi++) {
+			sp_end = std::min(m, sp0 + r.SPW * NB);
+			npanels = (sp_end - sp0 + NB - 1) / NB;
+			have_live = false;
+			live_rows = -1;
+			if ((spi == 1 || spi == 2 || (spi > 0 && spi % 4 == 0)) && finished())
+				break;
+			if (deficient) {
 				retire();
 				if (live_rows == 0)
 					break;                           // every row holds a pivot or is zero from here on
 			}
-			const int sp_end = std::min(m, sp0 + SPW * NB);
-			const int mrT = m - sp_end;              // columns beyond the super-panel
-			UpdSets S{};
-			int *abort_d = full_flag + 12;          // optimistic super-panels: raised by a try that cannot finish its panel
-			hipEvent_t wait_before_update = nullptr;          // (phase 2: the update kernel waits for this event -- the lookahead has read A)
-			bool abort_by_panel = false;                      // (passes with the tries one panel ahead: see BlockGjArgs::abort_words)
-			// hand-off words of such a pass (handoff_wait / handoff_signal): by panel, the try is through / workgroups of the lookahead / of the update
-			int *hand_try = use_ahead ? reinterpret_cast<int *>(alt_tile + (size_t) 2 * NB * NB) : nullptr, *hand_look = hand_try + MAXSETS, *hand_upd = hand_try + 2 * MAXSETS;
-			int upd_workgroups[MAXSETS] = {};
-			bool look_follows = false;                        // (phase 2 of a panel whose lookahead runs: the update waits for it)
-			int *abort_pp = full_flag + 16;
-			auto run_panel = [&](int c0, int nsets, bool optimistic, int phase = 0, bool with_alt = false) {
-				hipStream_t stream_keep = stream;
-				hipStream_t stream = (phase == 1) ? ahead.s_try : stream_keep;          // (the launches below name `stream`)
-				const int *abort_c = optimistic ? (abort_by_panel ? abort_pp + nsets : abort_d) : nullptr;
-				const int par = nsets & 1;          // (Ginv, gamma, cand_pivot: two copies -- the try of panel i + 1 may run beside the multipliers of panel i)
-				const int width = std::min(NB, m - c0);
-				// (sets alternate between two halves by super-panel: the far update of the previous super-panel may
-				//  still be reading its multipliers on the second stream)
-				const int slot = (spi & 1) * MAXSETS + nsets;
-				uint32_t *P_s = P4 + (size_t) slot * (size_t) n * PW;
-				int *rho_s = rho4 + slot * NB, *knew_s = knew4 + slot * 16;
-				// (regular panel of a block on which the tries fail: straight to the tournament, three launches fewer)
-				const bool straight = !optimistic && have_live;
-				if (!optimistic && !straight)
-					hipLaunchKernelGGL(rref_first_free, dim3(1), dim3(64), 0, stream, flags, n, free_count + 4, first64, free_count + 2, have_live ? live_list : nullptr,
-					                   free_count + 10);
-				// Gauss-Jordan straight on the first 64 free rows (try mode): when they give a pivot in every column of the
-				// panel (the usual case while the block is not exhausted) everything up to the regular call returns at once
-				BlockGjArgs bg;
-				bg.A = dA;
-				bg.ld = ld;
-				bg.n = n;
-				bg.c0 = c0;
-				bg.width = width;
-				bg.cand = nullptr;
-				bg.cand_first = cand_first;
-				bg.full = full_flag;
-				bg.Ginv = Ginv + (size_t) par * NB * NB;
-				bg.gamma = gamma + par * NB;
-				bg.is_pivot_row = flags;
-				bg.pivrow = pivrow;
-				bg.pivcol = d_pivcol;
-				bg.rank = rank_d;
-				bg.knew = knew_s;
-				bg.rho = rho_s;
-				bg.cand_pivot = cand_pivot + par * NB;
-				bg.F = F;
-				bg.invtab = invtab;
-				bg.mode = 1;
-				bg.try_rows = first64;
-				bg.try_count = free_count + 2;
-				bg.gj_done = full_flag + 4;
-				bg.try_state = full_flag + 8;
-				bg.panel_index = c0 / NB;
-				bg.abort = optimistic ? const_cast<int *>(abort_c) : nullptr;
-				bg.abort_value = nsets;
-				bg.abort_words = (optimistic && abort_by_panel) ? abort_pp : nullptr;
-				bg.abort_summary = abort_d;
-				bg.abort_count = MAXSETS;
-				bg.ff_flags = optimistic ? flags : nullptr;
-				bg.ff_hint = free_count + 4;
-				bg.ff_out = first64;
-				bg.ff_count = free_count + 2;
-				bg.live_list = have_live ? live_list : nullptr;
-				bg.live_count = free_count + 10;
-				bg.alt = nullptr;
-				bg.done_word = (phase == 1) ? hand_try + nsets : nullptr;
-				if (with_alt) {
-					bg.alt = alt_tile + (size_t) (nsets & 1) * NB * NB;
-					bg.ff_flags = nullptr;          // (rref_lookahead picked the candidates: first64 / free_count + 2)
-				}
-				// (a block on which tries fail -- dependent columns, or rows that depend on each other --: the try that takes what its
-				//  candidates give, with the proof in the multiplier kernel; see BlockGjArgs)
-				const bool take_what_comes = optimistic && have_live && small_prime && small16 && mfma_ok && width == NB;
-				if (phase == 2) {
-					;                                // (the try ran on its own stream)
-				} else if (take_what_comes) {
-					bg.mode = 2;
-					hipLaunchKernelGGL((rref_block_gj<true, 8>), dim3(1), dim3(1024), invtab_bytes, stream, bg);
-					bg.mode = 1;
-				} else if (try_first && !straight) {
-					if (fast_try)
-						hipLaunchKernelGGL(rref_try_inverse, dim3(1), dim3(256), invtab_bytes, stream, bg);
-					else if (small_prime)
-						hipLaunchKernelGGL((rref_block_gj<true, 8>), dim3(1), dim3(1024), invtab_bytes, stream, bg);
-					else
-						hipLaunchKernelGGL((rref_block_gj<false, 8>), dim3(1), dim3(1024), 0, stream, bg);
-				}
-				if (phase == 1)
-					return;
-				if (!optimistic) {
-				// the first 64 free rows alone, by selection (when the try was skipped or failed)
-				if (straight)
-					;
-				else if (small_prime)
-					hipLaunchKernelGGL(rref_select_first<true>, dim3(1), dim3(256), 0, stream, dA, ld, c0, width, first64, free_count + 2,
-					                   cand_first, F, full_flag, full_flag + 4);
-				else
-					hipLaunchKernelGGL(rref_select_first<false>, dim3(1), dim3(256), 0, stream, dA, ld, c0, width, first64, free_count + 2,
-					                   cand_first, F, full_flag, full_flag + 4);
-				// (everything from here to the Gauss-Jordan block returns at once when that was enough)
-				hipLaunchKernelGGL(rref_free_list, dim3(1), dim3(1024), 0, stream, flags, n, candA, free_count, full_flag, straight ? full_flag : nullptr);
-				int n_in = have_live ? std::max(live_rows, 1) : n;          // (the free rows are among the live ones: fewer levels on a block that is running out)
-				const int *count_dev = free_count;
-				int *src = candA, *dst = candB;
-				for (;;) {
-					const int wgs = (n_in + SEL_ROWS - 1) / SEL_ROWS;
-					if (small_prime)
-						hipLaunchKernelGGL(rref_select_kernel<true>, dim3(wgs), dim3(SEL_ROWS), 0, stream, dA, ld, c0, width, src, n_in,
-						                   count_dev, dst, F, full_flag, nullptr);
-					else
-						hipLaunchKernelGGL(rref_select_kernel<false>, dim3(wgs), dim3(SEL_ROWS), 0, stream, dA, ld, c0, width, src, n_in,
-						                   count_dev, dst, F, full_flag, nullptr);
-					// (the first level reads candA and writes candB; candA is then free)
-					std::swap(src, dst);
-					n_in = wgs * NB;
-					count_dev = nullptr;
-					if (wgs == 1)
-						break;
-				}
-				bg.cand = src;
-				bg.mode = 0;
-				if (small_prime)
-					hipLaunchKernelGGL((rref_block_gj<true, 8>), dim3(1), dim3(1024), invtab_bytes, stream, bg);
-				else
-					hipLaunchKernelGGL((rref_block_gj<false, 8>), dim3(1), dim3(1024), 0, stream, bg);
-				}
-				signed char *Mh_s = M8 + (size_t) slot * 2 * (size_t) n * 64, *Ml_s = Mh_s + (size_t) n * 64;
-				MultArgs ma{dA, ld, n, m, c0, Ginv + (size_t) par * NB * NB, gamma + par * NB, knew_s, P_s, F, rho_s, cand_pivot + par * NB, mfma_ok ? Mh_s : nullptr, mfma_ok ? Ml_s : nullptr,
-				            mfma_ok ? Zacc + (size_t) nsets * NB : nullptr /* M_s becomes block `nsets` of Z */, ldz, abort_c,
-				            take_what_comes ? flags : nullptr, abort_d, nsets, (phase == 2) ? hand_try + nsets : nullptr,
-				            (phase == 2 && look_follows) ? hand_look + nsets : nullptr, LOOK_WGS};
-				const int nmult = (n + 63) / 64;
-				// the columns of the super-panel, from this panel on, and (matrix cores) the multipliers of its earlier
-				// panels, blocks 0 .. nsets - 1 of Z: K = 64 update now
-				const int mr_sp = sp_end - c0;
-				UpdSets one{};
-				one.P[0] = P_s;
-				one.B[0] = B;
-				one.knew[0] = knew_s;
-				one.nsets = 1;
-				one.abort = abort_c;
-				int tiles = (mr_sp + 63) / 64;
-				if (mfma_ok) {
-					// multipliers and the digit planes of the pivot rows in one launch
-					const int tiles1 = (mr_sp + 63) / 64, mr2 = nsets * NB;
-					GatherArgs ga{dA, ld, c0, mr_sp, rho_s, knew_s, Bown_h, Bown_l, nullptr, F, Zacc, ldz, tiles1, mr2, abort_c};
-					const int ngather = (tiles1 * 64 + mr2 + 255) / 256;
-					if (small16)
-						hipLaunchKernelGGL(rref_mult_gather<true>, dim3(nmult + ngather), dim3(256), 0, stream, ma, ga, nmult);
-					else
-						hipLaunchKernelGGL(rref_mult_gather<false>, dim3(nmult + ngather), dim3(256), 0, stream, ma, ga, nmult);
-					one.Mh[0] = Mh_s;
-					one.Ml[0] = Ml_s;
-					one.Bh[0] = Bown_h;
-					one.Bl[0] = Bown_l;
-					if (mr2 > 0) {
-						one.Z2 = Zacc;
-						one.ld2 = ldz;
-						one.tiles1 = tiles1;
-						one.mr2 = mr2;
-						tiles = tiles1 + mr2 / 64;
-					}
-				} else {
-					if (small16)
-						hipLaunchKernelGGL(rref_multipliers<true>, dim3(nmult), dim3(256), 0, stream, ma);
-					else
-						hipLaunchKernelGGL(rref_multipliers<false>, dim3(nmult), dim3(256), 0, stream, ma);
-					hipLaunchKernelGGL(rref_gather_pivot_rows, dim3(512), dim3(256), 0, stream, dA, ld, c0, mr_sp, rho_s, knew_s, B);
-				}
-				if (wait_before_update != nullptr)
-					HIP_CHECK(hipStreamWaitEvent(stream, wait_before_update, 0));
-				if (phase == 2) {
-					one.done_word = hand_upd + nsets;
-					upd_workgroups[nsets] = tiles * ((n + 63) / 64);
-				}
-				timed([&]() {
-					dim3 grid(tiles, (n + 63) / 64);
-					if (mfma_ok)
-						hipLaunchKernelGGL(rref_update_mfma_multi, grid, dim3(256), 0, stream, dA, ld, n, c0, mr_sp, one, F);
-					else
-						hipLaunchKernelGGL(rref_update_valu, grid, dim3(256), 0, stream, dA, ld, n, c0, mr_sp, P_s, B, knew_s, F);
-				});
-				set_P[nsets] = P_s;
-				set_rho[nsets] = rho_s;
-				set_knew[nsets] = knew_s;
-				set_Mh[nsets] = Mh_s;
-				set_Ml[nsets] = Ml_s;
-				HIP_CHECK(hipGetLastError());
-			};
-			// Optimistic pass: first-free rows, try, multipliers, update -- five launches per panel instead of twelve, none of
-			// the selection kernels (they return at once when the try succeeds, but a launch is a launch: 30 us per panel).
-			// The host looks at the flag once per super-panel; the panels from the one that raised it on are redone the
-			// regular way, and the next super-panel is not attempted optimistically.
-			const int npanels = (sp_end - sp0 + NB - 1) / NB;
+			// optimistic passes (not in a timed call): the panels from the one that gave up on are done the regular way, and
+			// the next super-panel is not attempted optimistically unless the rows are being retired
 			int first_regular = 0;
-			if (optimistic_ok && fast_try && mfma_ok && try_first && ms_update == nullptr) {
-				// passes of optimistic panel steps from `start` on; a pass ends at the panel whose try (or proof) failed.  The first
-				// failure of a call switches to the tries that take what comes (rows retired, candidates spread: BlockGjArgs mode 2)
-				// and the pass is taken up again at that panel; a failure in that mode sends the one panel the regular way.
-				int start = 0, fallbacks = 0;
-				while (start < npanels) {
-					HIP_CHECK(hipMemsetAsync(abort_d, 0, sizeof(int), stream));
-					// (knew[1] of a slot = the pivots a mode-2 try has taken, for rref_rollback: nothing yet)
-					HIP_CHECK(hipMemset2DAsync(knew4 + (size_t) (spi & 1) * MAXSETS * 16 + 1, 16 * sizeof(int), 0, sizeof(int), MAXSETS, stream));
-					// one panel ahead: plain optimistic passes only (full panels, no list of live rows, p < 2^16)
-					// (... and blocks of at most 6,144 rows: beyond, the multipliers and the update
-					//  of a panel take longer than its try -- the chain is no longer what the call waits for, and two streams of kernels that
-					//  poll each other only get in the way: 16,384 x 16,384 went from 40 to 53 ms with it)
-					const int look_rows = 6144;
-					const bool look = use_ahead && !have_live && small16 && npanels - start >= 2 && n <= look_rows;
-					if (!look) {
-						for (int i = start; i < npanels; i++)
-							run_panel(sp0 + i * NB, i, true);
-					} else {
-						abort_by_panel = true;
-						HIP_CHECK(hipMemsetAsync(abort_pp, 0, MAXSETS * sizeof(int), stream));
-						HIP_CHECK(hipMemsetAsync(hand_try, 0, 3 * MAXSETS * sizeof(int), stream));
-						HIP_CHECK(hipEventRecord(ahead.ev_start, stream));
-						HIP_CHECK(hipStreamWaitEvent(ahead.s_try, ahead.ev_start, 0));
-						// The try stream: try(start), look(start), try(start + 1), ... back to back, no event between them.  The main
-						// stream: multipliers(i) (its workgroups wait for try(i)'s word), update(i) (waits for look(i): it REWRITES the
-						// next panel's columns of the candidates and of the pivot rows, which look(i) reads), ...  look(i) waits for
-						// the workgroups of update(i - 1).  No cycle: every wait is for a kernel that is earlier in BOTH orders.
-						for (int i = start; i < npanels; i++) {
-							const int c0 = sp0 + i * NB;
-							run_panel(c0, i, true, 1, i > start);          // try(i): from A for the first panel of the pass, from look(i - 1)'s tile after that
-							const bool next_full = i + 1 < npanels && c0 + 2 * NB <= m;
-							if (next_full) {
-								const int slot = (spi & 1) * MAXSETS + i;
-								LookArgs la{dA, ld, n, c0, Ginv + (size_t) (i & 1) * NB * NB, rho4 + slot * NB, knew4 + slot * 16, flags, free_count + 4, first64, free_count + 2,
-								            alt_tile + (size_t) ((i + 1) & 1) * NB * NB, abort_pp + i, (i > start) ? hand_upd + (i - 1) : nullptr, (i > start) ? upd_workgroups[i - 1] : 0,
-								            hand_look + i, F};
-								hipLaunchKernelGGL(rref_lookahead, dim3(LOOK_WGS), dim3(256), 0, ahead.s_try, la);
-							}
-							look_follows = next_full;
-							run_panel(c0, i, true, 2);
-							look_follows = false;
-							if (!next_full && i + 1 < npanels) {
-								// (a narrow last panel: its try reads A itself, after update(i))
-								HIP_CHECK(hipEventRecord(ahead.ev_upd[i], stream));
-								HIP_CHECK(hipStreamWaitEvent(ahead.s_try, ahead.ev_upd[i], 0));
-							}
-						}
-						abort_by_panel = false;
-					}
-					int raised = 0;
-					HIP_CHECK(hipMemcpyAsync(&raised, abort_d, sizeof(int), hipMemcpyDeviceToHost, stream));
-					HIP_CHECK(hipStreamSynchronize(stream));
-					const int stop = raised != 0 ? raised - 1 : npanels;
-					stat_opt_ok += stop - start;
-					start = stop;
-					if (raised == 0)
-						break;
-					stat_aborts += 1;
-					if (have_live) {
-						// (a mode-2 try whose proof failed has taken its pivots already: they go back before the panel is redone)
-						const int slot = (spi & 1) * MAXSETS + stop;
-						if (sh::env_get("SPASM_HIP_RREF_TIMING")) {
-							int took = 0, tc = 0;
-							HIP_CHECK(hipMemcpy(&took, knew4 + slot * 16 + 1, sizeof(int), hipMemcpyDeviceToHost));
-							HIP_CHECK(hipMemcpy(&tc, free_count + 2, sizeof(int), hipMemcpyDeviceToHost));
-							fprintf(stderr, "[rref timing] super-panel %d: the try of panel %d took %d pivots from %d candidates (%d live rows) and the proof failed\n", spi, stop, took, tc,
-							        live_rows);
-						}
-						hipLaunchKernelGGL(rref_rollback, dim3(1), dim3(64), 0, stream, rho4 + slot * NB, knew4 + slot * 16, flags, rank_d);
-						run_panel(sp0 + stop * NB, stop, false);
-						stat_regular += 1;
-						start = stop + 1;
-						fallbacks += 1;
-						if (fallbacks >= 3)
-							break;                   // (the rest of the super-panel the regular way)
-					} else if (retire_rows && small_prime && small16) {
-						deficient = true;
-						retire();
-					} else {
-						break;
-					}
-				}
-				first_regular = start;
-				if (start < npanels)
-					optimistic_skip = (deficient && retire_rows) ? 0 : 2;          // (2: the next super-panel is not attempted)
+			if (optimistic_skip == 0 && r.fast_try && r.mfma_ok && !r.timed) {
+				first_regular = optimistic_passes();
+				if (first_regular < npanels)
+					optimistic_skip = deficient ? 0 : 2;
 			}
 			if (optimistic_skip > 0)
 				optimistic_skip -= 1;
-			optimistic_ok = optimistic_enabled && optimistic_skip == 0;
 			for (int i = first_regular; i < npanels; i++)
-				run_panel(sp0 + i * NB, i, false);
+				regular_panel(i);
 			stat_regular += npanels - first_regular;
 			stat_marked += have_live;
-			const int nsets = npanels;
-			if (mrT > 0) {
-				// beyond the super-panel.  What is read here -- the rows rho_i beyond the super-panel -- is written by the far
-				// update of the previous super-panel on the second stream: wait for it here, not earlier -- the panel steps
-				// above (latency-bound, one workgroup most of the time) ran beside it.
-				if (far_pending)
-					HIP_CHECK(hipStreamWaitEvent(stream, ev_far, 0));
-				if (mfma_ok) {
-					// C += sum_i M'_i C[rho_i]: M'_i = block i of Z (digit planes), C[rho_i] = the rows as they stand
-					signed char *MZ = M8 + (size_t) (2 * MAXSETS + (spi & 1) * MAXSETS) * 2 * (size_t) n * 64;
-					hipLaunchKernelGGL(rref_split_Z, dim3((n + 63) / 64, nsets), dim3(256), 0, stream, Zacc, ldz, n, nsets, MZ, (int64_t) 2 * n * 64, F);
-					GatherSets gs{};
-					for (int s = 0; s < nsets; s++) {
-						signed char *Bh_s = B8 + (size_t) s * 2 * (size_t) m * 64, *Bl_s = Bh_s + (size_t) m * 64;
-						gs.rho[s] = set_rho[s];
-						gs.knew[s] = set_knew[s];
-						gs.Bh[s] = Bh_s;
-						gs.Bl[s] = Bl_s;
-						S.knew[s] = set_knew[s];
-						S.Mh[s] = MZ + (size_t) s * 2 * (size_t) n * 64;
-						S.Ml[s] = S.Mh[s] + (size_t) n * 64;
-						S.Bh[s] = Bh_s;
-						S.Bl[s] = Bl_s;
-					}
-					hipLaunchKernelGGL(rref_gather_split_sets, dim3((mrT + 255) / 256, nsets), dim3(256), 0, stream, dA, ld, sp_end, mrT, gs, F);
-				} else {
-					for (int s = 0; s < nsets; s++) {
-						S.nsets = s;          // the sets before this one
-						uint32_t *Bt_s = Bt4 + (size_t) s * (size_t) NB * (size_t) m;
-						dim3 grid((mrT + 255) / 256, NB);
-						if (small16)
-							hipLaunchKernelGGL(rref_trailing_B<true>, grid, dim3(256), 0, stream, dA, ld, n, sp_end, mrT, S, set_rho[s], set_knew[s], Bt_s, F);
-						else
-							hipLaunchKernelGGL(rref_trailing_B<false>, grid, dim3(256), 0, stream, dA, ld, n, sp_end, mrT, S, set_rho[s], set_knew[s], Bt_s, F);
-						S.P[s] = set_P[s];
-						S.B[s] = Bt_s;
-						S.knew[s] = set_knew[s];
-					}
-				}
-				S.nsets = nsets;
-				// near part (the next super-panel's own columns) on this stream, far part on the second one
-				const int near = (mfma_ok && stream2 != nullptr) ? std::min(mrT, SPW * NB) : mrT;
-				// (a 64 x 128 tile kernel, two waves per SIMD, 256 registers, was built in round 5 and took 24 % less serialised time for the
-				//  updates -- and 5 % MORE for the call, with and without the lookahead of round 6: removed.  Round 6 also built a 128 x 128
-				//  tile kernel for the far part -- 64 x 64 per wave, three accumulators per 32 x 32 tile, half the LDS bytes per matrix
-				//  instruction, operands read one phase ahead, two LDS buffers, ONE workgroup per CU (320 registers): bit-identical and no
-				//  faster, 5.08 against 5.00 ms serialised.  With K = 512 a workgroup is prologue (its 64 KB of C, the first planes),
-				//  eight short sets whose planes arrive later than the 0.43 us the set before takes to multiply, and an epilogue; with one
-				//  workgroup per CU these phases have nothing to hide behind.  What the far update needs is several workgroups per CU in
-				//  different phases, which is what the 64 x 64 kernel has: NOTES/round6.md.)
-				timed([&]() {
-					dim3 grid((near + 63) / 64, (n + 63) / 64);
-					if (mfma_ok) {
-						hipLaunchKernelGGL(rref_update_mfma_multi, grid, dim3(256), 0, stream, dA, ld, n, sp_end, near, S, F);
-					} else {
-						for (int s = 0; s < nsets; s++)
-							hipLaunchKernelGGL(rref_update_valu, grid, dim3(256), 0, stream, dA, ld, n, sp_end, mrT, S.P[s], S.B[s], S.knew[s], F);
-					}
-				});
-				far_pending = false;
-				if (near < mrT) {
-					UpdSets Sf = S;
-					for (int s = 0; s < nsets; s++) {
-						Sf.Bh[s] = S.Bh[s] + (size_t) near * 64;
-						Sf.Bl[s] = S.Bl[s] + (size_t) near * 64;
-					}
-					HIP_CHECK(hipEventRecord(ev_near, stream));
-					HIP_CHECK(hipStreamWaitEvent(stream2, ev_near, 0));
-					dim3 grid((mrT - near + 63) / 64, (n + 63) / 64);
-					if (ms_update != nullptr)
-						HIP_CHECK(hipEventRecord(e0, stream2));
-					hipLaunchKernelGGL(rref_update_mfma_multi, grid, dim3(256), 0, stream2, dA, ld, n, sp_end + near, mrT - near, Sf, F);
-					HIP_CHECK(hipEventRecord(ev_far, stream2));
-					far_pending = true;
-					if (ms_update != nullptr) {          // (timing runs serialise the two streams)
-						HIP_CHECK(hipEventSynchronize(ev_far));
-						float ms;
-						HIP_CHECK(hipEventElapsedTime(&ms, e0, ev_far));
-						total_update += ms;
-					}
-				}
-				HIP_CHECK(hipGetLastError());
-			}
+			if (sp_end < m)
+				far_update();
 		}
 		if (far_pending)
-			HIP_CHECK(hipStreamWaitEvent(stream, ev_far, 0));
-	} else {
-		for (int c0 = 0; c0 < m; c0 += NB) {
-			if (c0 > 0 && (c0 / NB) % 8 == 0) {           // every row already holds a pivot: the rest is reduced
-				int rk = 0;
-				HIP_CHECK(hipMemcpyAsync(&rk, rank_d, sizeof(int), hipMemcpyDeviceToHost, stream));
-				HIP_CHECK(hipStreamSynchronize(stream));
-				if (rk >= n)
-					break;
-			}
-			const int width = (m - c0 < NB) ? m - c0 : NB;
-			PanelArgs g;
-			g.A = dA;
-			g.ld = ld;
-			g.n = n;
-			g.m = m;
-			g.c0 = c0;
-			g.width = width;
-			g.P = P;
-			g.is_pivot_row = flags;
-			g.pivrow = pivrow;
-			g.pivcol = d_pivcol;
-			g.rank = rank_d;
-			g.knew = knew;
-			g.rho = rho;
-			g.F = F;
-			if (n >= coop_min_rows) {
-				CoopPanelArgs ca;
-				ca.g = g;
-				ca.barrier = coop_barrier;
-				ca.cand = coop_cand;
-				ca.err = coop_err;
-				HIP_CHECK(hipMemsetAsync(coop_barrier, 0, sizeof(unsigned int), stream));
-				HIP_CHECK(hipMemsetAsync(coop_cand, 0x7F, NB * sizeof(int), stream));     // 0x7F7F7F7F >= any row index
-				int G = (n + COOP_THREADS - 1) / COOP_THREADS;
-				if (G > 64)
-					G = 64;
-				hipLaunchKernelGGL(rref_panel_coop_kernel, dim3(G), dim3(COOP_THREADS), 0, stream, ca);
-			} else {
-				hipLaunchKernelGGL(rref_panel_kernel, dim3(1), dim3(PANEL_THREADS), 0, stream, g);
-			}
-			const int c1 = c0 + width;
-			const int mr = m - c1;
-			if (mr > 0) {
-				hipLaunchKernelGGL(rref_gather_pivot_rows, dim3(512), dim3(256), 0, stream, dA, ld, c1, mr, rho, knew, B);
-				dim3 grid((mr + 63) / 64, (n + 63) / 64);
-				if (ms_update != nullptr)
-					HIP_CHECK(hipEventRecord(e0, stream));
-				if (mfma_ok)
-					hipLaunchKernelGGL(rref_update_mfma, grid, dim3(256), 0, stream, dA, ld, n, c1, mr, P, B, knew, F);
-				else
-					hipLaunchKernelGGL(rref_update_valu, grid, dim3(256), 0, stream, dA, ld, n, c1, mr, P, B, knew, F);
-				if (ms_update != nullptr) {
-					HIP_CHECK(hipEventRecord(e1, stream));
-					HIP_CHECK(hipEventSynchronize(e1));
-					float ms;
-					HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
-					total_update += ms;
-				}
-			}
-			HIP_CHECK(hipGetLastError());
-		}
+			HIP_CHECK(hipStreamWaitEvent(stream, st->ev_far, 0));
 	}
-	double t_loop = 0.0;
-	if (sh::env_get("SPASM_HIP_RREF_TIMING")) {
+};
+
+// Echelon rows to the top, in pivot-column order: through TMP (rank x m), which takes the room of the panel buffers.
+void rref_rows_to_top(const RrefCall &c, RrefWorkspace &ws, int rank)
+{
+	ws.release(ws.CAND_A);
+	uint32_t *tmp = ws.take<uint32_t>(ws.TMP, (size_t) rank * (size_t) c.m * sizeof(uint32_t));
+	hipLaunchKernelGGL(rref_rows_to_tmp, dim3(std::min(rank, 4096)), dim3(256), 0, c.stream, c.A, c.ld, c.m, c.pivrow, rank, tmp);
+	hipLaunchKernelGGL(rref_tmp_to_rows, dim3(std::min(c.n, 4096)), dim3(256), 0, c.stream, c.A, c.ld, c.n, c.m, rank, tmp, c.pivrow);
+	HIP_CHECK(hipStreamSynchronize(c.stream));
+	ws.release(ws.TMP);
+}
+
+}  // namespace
+
+int device_rref(int64_t prime, int n, int m, uint32_t *dA, int64_t ld, int *d_pivcol, hipStream_t stream, int use_mfma, float *ms_update)
+{
+	if (n == 0 || m == 0)
+		return 0;
+	const double t_entry = wtime();
+	// 1. set up: the route, the buffers (flags, rank, ... zeroed on the stream), the streams
+	RrefWorkspace ws;
+	UpdateTimer timer(ms_update != nullptr);
+	RrefCall c{dA, ld, n, m, d_pivcol, nullptr, nullptr, nullptr, nullptr, stream, to_dev(mont_setup(prime)), rref_route(prime, use_mfma, ms_update != nullptr), &timer};
+	c.B = ws.take<uint32_t>(ws.PIVOT_ROWS, (size_t) NB * (size_t) m * sizeof(uint32_t));
+	c.flags = ws.take<int>(ws.FLAGS, (size_t) n * sizeof(int));
+	c.pivrow = ws.take<int>(ws.PIVROW, (size_t) std::min(n, m) * sizeof(int) + 64);
+	c.rank_d = ws.take<int>(ws.RANK, 64);
+	HIP_CHECK(hipMemsetAsync(c.flags, 0, (size_t) n * sizeof(int), stream));
+	HIP_CHECK(hipMemsetAsync(c.rank_d, 0, 64, stream));
+	std::optional<TournamentRref> T;          // (the column route has none)
+	if (c.r.tournament) {
+		T.emplace(c);
+		T->take_buffers(ws, prime);
+	}
+	int *coop_err = ws.take<int>(ws.COOP_ERR, 64);
+	HIP_CHECK(hipMemsetAsync(coop_err, 0, 64, stream));
+	if (T && (T->r.use_ahead || T->r.two_streams)) {
+		T->st = &rref_streams(stream, ws, &T->r.use_ahead);
+		if (T->r.use_ahead)
+			T->take_lookahead_buffers(ws);
+	}
+	if (c.r.timing) {
 		HIP_CHECK(hipStreamSynchronize(stream));
-		if (stream2 != nullptr)
-			HIP_CHECK(hipStreamSynchronize(stream2));
-		t_loop = wtime();
+		fprintf(stderr, "[rref timing] allocations + setup: %.3f ms\n", 1e3 * (wtime() - t_entry));
+	}
+	// 2. the panels
+	if (T)
+		T->run();
+	else
+		rref_by_columns(c, ws, coop_err);
+	if (c.r.timing) {
+		HIP_CHECK(hipStreamSynchronize(stream));
+		if (c.r.two_streams)
+			HIP_CHECK(hipStreamSynchronize(T->st->s_far));
 		fprintf(stderr, "[rref timing] up to the end of the panels: %.3f ms (%d panels by the optimistic passes, %d the regular way, %d super-panels gave up, %d with retired rows)\n",
-		        1e3 * (t_loop - t_entry), stat_opt_ok, stat_regular, stat_aborts, stat_marked);
+		        1e3 * (wtime() - t_entry), T ? T->stat_opt_ok : 0, T ? T->stat_regular : 0, T ? T->stat_aborts : 0, T ? T->stat_marked : 0);
 	}
-	int rank = 0, coop_failed = 0;
-	HIP_CHECK(hipMemcpyAsync(&rank, rank_d, sizeof(int), hipMemcpyDeviceToHost, stream));
-	if (stream2 != nullptr) {
-		HIP_CHECK(hipStreamSynchronize(stream2));          // (the stream itself is kept for the next call)
-		(void) hipEventDestroy(ev_near);
-		(void) hipEventDestroy(ev_far);
-	}
+	int rank = 0, coop_failed = 0, stuck = 0;
+	HIP_CHECK(hipMemcpyAsync(&rank, c.rank_d, sizeof(int), hipMemcpyDeviceToHost, stream));
+	if (c.r.two_streams)
+		HIP_CHECK(hipStreamSynchronize(T->st->s_far));          // (the stream itself is kept for the next call)
 	HIP_CHECK(hipMemcpyAsync(&coop_failed, coop_err, sizeof(int), hipMemcpyDeviceToHost, stream));
-	int stuck = 0;
-	if (use_ahead)
+	if (T && T->r.use_ahead)          // (after the probe: a lookahead pass may have run)
 		HIP_CHECK(hipMemcpyFromSymbolAsync(&stuck, HIP_SYMBOL(g_handoff_stuck), sizeof(int), 0, hipMemcpyDeviceToHost, stream));
 	HIP_CHECK(hipStreamSynchronize(stream));
 	if (stuck) {
 		const int zero = 0;
 		HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_handoff_stuck), &zero, sizeof(int)));
 	}
-	if (tournament) {
-		ws_free(candA);
-		ws_free(candB);
-		ws_free(free_count);
-		ws_free(gamma);
-		ws_free(cand_first);
-		ws_free(first64);
-		ws_free(live_list);
-		ws_free(cand_pivot);
-		ws_free(P4);
-		ws_free(Bt4);
-		ws_free(Zacc);
-		ws_free(rho4);
-		ws_free(M8);
-		ws_free(invtab);
-		ws_free(B8);
-		ws_free(knew4);
-		ws_free(full_flag);
-		ws_free(Ginv);
-	}
-	ws_free(coop_barrier);
-	ws_free(coop_cand);
-	ws_free(coop_err);
 	if (coop_failed)
 		die("dense RREF: a grid-wide barrier timed out (cooperative panel kernel)");
 	if (stuck)
 		die("dense RREF: a hand-off between the two streams of a lookahead pass timed out (SPASM_HIP_EXPERIMENT=1 SPASM_HIP_RREF_LOOKAHEAD=0 runs without them)");
-	if (rank > 0) {
-		uint32_t *tmp = nullptr;
-		ws_malloc((void **) &tmp, (size_t) rank * (size_t) m * sizeof(uint32_t));
-		hipLaunchKernelGGL(rref_rows_to_tmp, dim3(std::min(rank, 4096)), dim3(256), 0, stream, dA, ld, m, pivrow, rank, tmp);
-		hipLaunchKernelGGL(rref_tmp_to_rows, dim3(std::min(n, 4096)), dim3(256), 0, stream, dA, ld, n, m, rank, tmp, pivrow);
-		HIP_CHECK(hipStreamSynchronize(stream));
-		ws_free(tmp);
-	}
-	if (ms_update != nullptr) {
-		*ms_update = total_update;
-		(void) hipEventDestroy(e0);
-		(void) hipEventDestroy(e1);
-	}
-	ws_free(P);
-	ws_free(B);
-	ws_free(flags);
-	ws_free(pivrow);
-	ws_free(rank_d);
-	ws_free(knew);
-	ws_free(rho);
-	if (sh::env_get("SPASM_HIP_RREF_TIMING"))
+	// 3. the final permutation, 4. the report
+	if (rank > 0)
+		rref_rows_to_top(c, ws, rank);
+	if (ms_update != nullptr)
+		*ms_update = timer.total;
+	if (c.r.timing)
 		fprintf(stderr, "[rref timing] whole call: %.3f ms\n", 1e3 * (wtime() - t_entry));
 	return rank;
 }
@@ -3210,12 +3222,7 @@ int device_echelon_extend(int64_t prime, int m, uint32_t *dM, int64_t ld, int k,
 		HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&rowpanel_window), hipFuncAttributeMaxDynamicSharedMemorySize, (int) win_lds));
 		configured = true;
 	}
-	auto planes_of_set = [&](int s, signed char *&Mh, signed char *&Ml, signed char *&Bh, signed char *&Bl) {
-		Mh = Mplanes + (size_t) s * 2 * n * 64;
-		Ml = Mh + (size_t) n * 64;
-		Bh = Bplanes + (size_t) s * 2 * (size_t) m * 64;
-		Bl = Bh + (size_t) m * 64;
-	};
+	const DigitPlanes planes{Mplanes, Bplanes, (size_t) n, (size_t) m};
 
 	const double t_start = wtime();
 	int total_iters = 0;
@@ -3232,13 +3239,13 @@ int device_echelon_extend(int64_t prime, int m, uint32_t *dM, int64_t ld, int k,
 		HIP_CHECK(hipMemcpyAsync(d_cnt, cnt.data(), SETS * sizeof(int), hipMemcpyHostToDevice, stream));
 		// (the planes of M for n = Sn rows: the first Sn * 64 bytes of each half)
 		hipLaunchKernelGGL(rref_split_Z, dim3((Sn + 63) / 64, nsets), dim3(256), 0, stream, Z, ldz, Sn, nsets, Mplanes, (int64_t) 2 * Sn * 64, F);
+		const DigitPlanes of_Y{Mplanes, Bplanes, (size_t) Sn, (size_t) m};
 		for (int s = 0; s < nsets; s++) {
-			signed char *Bh = Bplanes + (size_t) s * 2 * (size_t) m * 64, *Bl = Bh + (size_t) m * 64;
-			hipLaunchKernelGGL(rref_split_B, dim3((m + 255) / 256), dim3(256), 0, stream, dM + (int64_t) (t0 + 64 * s) * ld, ld, m, d_cnt + s, Bh, Bl, F);
-			S.Mh[s] = Mplanes + (size_t) s * 2 * Sn * 64;
-			S.Ml[s] = S.Mh[s] + (size_t) Sn * 64;
-			S.Bh[s] = Bh;
-			S.Bl[s] = Bl;
+			hipLaunchKernelGGL(rref_split_B, dim3((m + 255) / 256), dim3(256), 0, stream, dM + (int64_t) (t0 + 64 * s) * ld, ld, m, d_cnt + s, of_Y.Bh(s), of_Y.Bl(s), F);
+			S.Mh[s] = of_Y.Mh(s);
+			S.Ml[s] = of_Y.Ml(s);
+			S.Bh[s] = of_Y.Bh(s);
+			S.Bl[s] = of_Y.Bl(s);
 		}
 		S.nsets = nsets;
 		hipLaunchKernelGGL(rref_update_mfma_multi, dim3((m + 63) / 64, (Sn + 63) / 64), dim3(256), 0, stream, Y, ld, Sn, 0, m, S, F);
@@ -3279,21 +3286,18 @@ int device_echelon_extend(int64_t prime, int m, uint32_t *dM, int64_t ld, int k,
 	bool found_since_check = false;
 	const bool all_zero_at_start = rest_is_zero(0);
 	auto split_panel = [&](int row0, int set) {          // the rows [row0, row0 + 64) of Y as the B planes of `set`
-		signed char *Mh, *Ml, *Bh, *Bl;
-		planes_of_set(set, Mh, Ml, Bh, Bl);
-		hipLaunchKernelGGL(rref_split_B, dim3((m + 255) / 256), dim3(256), 0, stream, Y + (int64_t) row0 * ld, ld, m, d_cnt + (Sn - row0 >= RP_ROWS ? 0 : 1), Bh, Bl, F);
+		hipLaunchKernelGGL(rref_split_B, dim3((m + 255) / 256), dim3(256), 0, stream, Y + (int64_t) row0 * ld, ld, m, d_cnt + (Sn - row0 >= RP_ROWS ? 0 : 1), planes.Bh(set),
+		                   planes.Bl(set), F);
 	};
 	auto clear_columns = [&](uint32_t *C, int rows, int skip_lo, int skip_hi, const int *piv, int nsets) {          // C -= C[:, piv] * (B planes of the sets)
 		hipLaunchKernelGGL(rowpanel_neg_columns, dim3((rows + 63) / 64, nsets), dim3(256), 0, stream, C, ld, rows, skip_lo, skip_hi, piv, Mplanes, (int64_t) 2 * n * 64,
 		                   (int64_t) n * 64, F);
 		UpdSets S{};
 		for (int s = 0; s < nsets; s++) {
-			signed char *Mh, *Ml, *Bh, *Bl;
-			planes_of_set(s, Mh, Ml, Bh, Bl);
-			S.Mh[s] = Mh;
-			S.Ml[s] = Ml;
-			S.Bh[s] = Bh;
-			S.Bl[s] = Bl;
+			S.Mh[s] = planes.Mh(s);
+			S.Ml[s] = planes.Ml(s);
+			S.Bh[s] = planes.Bh(s);
+			S.Bl[s] = planes.Bl(s);
 		}
 		S.nsets = nsets;
 		hipLaunchKernelGGL(rref_update_mfma_multi, dim3((m + 63) / 64, (rows + 63) / 64), dim3(256), 0, stream, C, ld, rows, 0, m, S, F);
@@ -3339,11 +3343,9 @@ int device_echelon_extend(int64_t prime, int m, uint32_t *dM, int64_t ld, int k,
 			const int last = count - RP_ROWS * (nsets - 1);
 			HIP_CHECK(hipMemcpyAsync(d_pad, pad.data(), pad.size() * sizeof(int), hipMemcpyHostToDevice, stream));
 			HIP_CHECK(hipMemcpyAsync(d_cnt + 2, &last, sizeof(int), hipMemcpyHostToDevice, stream));
-			for (int s2 = 0; s2 < nsets; s2++) {
-				signed char *Mh, *Ml, *Bh, *Bl;
-				planes_of_set(s2, Mh, Ml, Bh, Bl);
-				hipLaunchKernelGGL(rref_split_B, dim3((m + 255) / 256), dim3(256), 0, stream, Yr + (int64_t) (t0 + RP_ROWS * s2) * ld, ld, m, d_cnt + (s2 + 1 < nsets ? 0 : 2), Bh, Bl, F);
-			}
+			for (int s2 = 0; s2 < nsets; s2++)
+				hipLaunchKernelGGL(rref_split_B, dim3((m + 255) / 256), dim3(256), 0, stream, Yr + (int64_t) (t0 + RP_ROWS * s2) * ld, ld, m, d_cnt + (s2 + 1 < nsets ? 0 : 2),
+				                   planes.Bh(s2), planes.Bl(s2), F);
 			clear_columns(dM, above, -1, -1, d_pad, nsets);
 			HIP_CHECK(hipStreamSynchronize(stream));          // (pad and last die here)
 			passes += 1;
@@ -3390,17 +3392,15 @@ int device_echelon_extend(int64_t prime, int m, uint32_t *dM, int64_t ld, int k,
 			if (iter > RP_ROWS + 2)
 				die("device_echelon_extend: a panel did not finish in %d window steps", iter);
 			// the OLD rows of the panel as digit planes, then T and the new pivots, then P <- T P
-			signed char *Mh, *Ml, *Bh, *Bl;
-			planes_of_set(0, Mh, Ml, Bh, Bl);
 			split_panel(r0, 0);
 			hipLaunchKernelGGL(rowpanel_window, dim3(1), dim3(RP_THREADS), win_lds, stream, P, ld, m, rows_here, d_left, d_state, d_newpiv, d_T, d_ispiv, F, d_invtab);
 			total_iters += 1;
-			hipLaunchKernelGGL(rowpanel_multipliers, dim3(1), dim3(256), 0, stream, P, ld, rows_here, 0, d_newpiv, d_T, Mh, Ml, F);
+			hipLaunchKernelGGL(rowpanel_multipliers, dim3(1), dim3(256), 0, stream, P, ld, rows_here, 0, d_newpiv, d_T, planes.Mh(0), planes.Ml(0), F);
 			UpdSets S{};
-			S.Mh[0] = Mh;
-			S.Ml[0] = Ml;
-			S.Bh[0] = Bh;
-			S.Bl[0] = Bl;
+			S.Mh[0] = planes.Mh(0);
+			S.Ml[0] = planes.Ml(0);
+			S.Bh[0] = planes.Bh(0);
+			S.Bl[0] = planes.Bl(0);
 			S.nsets = 1;
 			hipLaunchKernelGGL(rref_update_mfma_multi, dim3((m + 63) / 64, 1), dim3(256), 0, stream, P, ld, rows_here, 0, m, S, F);
 			look();

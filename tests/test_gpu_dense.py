@@ -41,8 +41,9 @@ def test_schur_dense_datatypes(oracle, dt):
     assert np.array_equal(S.astype(np.int64), want)
 
 
-def _check_rref(oracle, p, M):
-    r_want, R_want, q_want = oracle.dense_rref(p, M)
+def _check_rref(oracle, p, M, want=None):
+    """want: oracle.dense_rref(p, M), where the caller has it already"""
+    r_want, R_want, q_want = want if want is not None else oracle.dense_rref(p, M)
     r, R, q = spasm_amd.ffpack_rref(p, M)
     assert r == r_want
     assert np.array_equal(q, q_want)
@@ -124,6 +125,74 @@ def _mod_product(L, R, p):
     for c in range(0, L.shape[1], 64):
         out = (out + (Lf[:, c:c + 64] @ Rf[c:c + 64]).astype(np.int64)) % p
     return out
+
+
+def _low_rank_product(p, n, m, rank):
+    """L R mod p with the factors of test_rref_super_panels_and_streams (same generator, same draws); the product itself in
+    exact float64 chunks where p allows it, with Python integers otherwise"""
+    rng = np.random.default_rng(n + 3 * m)
+    k = min(rank, n, m)
+    L = rng.integers(0, p, size=(n, k), dtype=np.int64)
+    R = rng.integers(0, p, size=(k, m), dtype=np.int64)
+    if p < 65536:
+        return _mod_product(L, R, p)
+    return np.array((L.astype(object).dot(R.astype(object))) % p, dtype=np.int64)
+
+
+def test_rref_calls_of_different_shapes_and_routes_in_a_row(oracle, monkeypatch):
+    """One process, one thread, hence one set of kept work buffers: calls of different shapes, moduli and routes one after the
+    other, each against the oracle.  Every buffer is reused dirty, larger and smaller than the call before left it, across the
+    tournament route on the matrix cores (two super-panels with a far part at 700 x 1500), the VALU route (p >= 65280) and the
+    column-by-column route on buffers the tournament calls sized; the last call repeats the second after everything else."""
+    calls = [((130, 64), 64, 42013, {}),
+             ((700, 1500), 333, 42013, {}),
+             ((65, 129), 40, 65537, {}),
+             ((300, 2000), 300, 42013, {}),
+             ((300, 200), 150, 4294967291, {}),
+             ((200, 300), 200, 42013, {"SPASM_HIP_RREF_PANEL": "columns"}),
+             ((700, 1500), 333, 42013, {})]
+    known = {}
+    for (n, m), rank, p, env in calls:
+        key = (n, m, rank, p)
+        if key not in known:
+            M = _low_rank_product(p, n, m, rank)
+            known[key] = (M, oracle.dense_rref(p, M))
+        M, want = known[key]
+        for name, val in env.items():
+            monkeypatch.setenv(name, val)
+        _check_rref(oracle, p, M, want)
+        for name in env:
+            monkeypatch.delenv(name)
+
+
+@pytest.mark.parametrize("shape,rank", [((300, 2000), 300), ((700, 1500), 333)])
+def test_rref_timed_call_equals_the_untimed_call(shape, rank):
+    """spasm_hip_drref_timed takes every panel the regular way and serialises the two streams of the far update; the suite
+    only entered that route at 4,096 x 32,768.  Timed on the matrix cores, timed with VALU updates and untimed: the same
+    rank, the same pivot columns, an identical matrix, and an update time from both timed calls."""
+    import ctypes as C
+    import torch
+    p = 42013
+    n, m = shape
+    dev = torch.device("cuda:0")
+    M = torch.from_numpy(_low_rank_product(p, n, m, rank)).to(torch.int32).to(dev)
+    L = spasm_amd.lib()
+    results = []
+    for mfma in (1, 0, None):
+        A = M.clone().contiguous()
+        piv = torch.zeros(m, dtype=torch.int32, device=dev)
+        if mfma is None:
+            r = L.spasm_hip_drref(p, n, m, A.data_ptr(), m, piv.data_ptr(), 0)
+        else:
+            ms = C.c_float(0)
+            r = L.spasm_hip_drref_timed(p, n, m, A.data_ptr(), m, piv.data_ptr(), 0, mfma, C.byref(ms))
+            assert ms.value > 0
+        torch.cuda.synchronize()
+        results.append((r, piv[:r].clone(), A))
+    for r, J, R in results:
+        assert 0 < r == results[0][0] <= rank
+        assert torch.equal(J, results[0][1])
+        assert torch.equal(R, results[0][2])
 
 
 _BIG_RREF = {}
