@@ -333,6 +333,23 @@ struct spasm_hip_dfact {
 	mutable std::unique_ptr<sh::FactPlan> host_plan;
 };
 
+// The events of a workspace, by what they mark in a spasm_hip_dschur call (schur_api.hip).  Two slots carry two names each, for
+// routes that never run in the same call: EV_PATH_BEGIN (an image route starts its apply) = EV_GROUP_END (the row-group kernel
+// is done), and EV_APPLY_END (the sparse image's apply kernel is done) = EV_EXPAND_BEGIN (the staged dense output starts its
+// last expansion).
+enum SchurEvent {
+	EV_CALL_BEGIN,            // counters reset, nothing of the route launched yet
+	EV_ELIM_END,              // every row reduced
+	EV_FINALIZE_END,          // row pointers and sorted gather done: end of the call
+	EV_TIER0_END,             // per-row tiers: small LDS table done
+	EV_TIER1_END,             // ... large LDS table done (or skipped)
+	EV_PATH_BEGIN,
+	EV_GROUP_END = EV_PATH_BEGIN,
+	EV_APPLY_END,
+	EV_EXPAND_BEGIN = EV_APPLY_END,
+	EV_COUNT
+};
+
 struct spasm_hip_dwork {
 	int max_rows = 0, m = 0;
 	int64_t pool_cap = 0;
@@ -348,16 +365,14 @@ struct spasm_hip_dwork {
 	int64_t sortbuf_ints = 0;
 	int *d_Sj = nullptr, *d_Sx = nullptr;
 	uint32_t *d_stage = nullptr;                  // packed rows of the staged sparse output (backsolve.hip)
-	int64_t stage_bytes = 0;
+	int64_t stage_words = 0;
 	uint64_t *d_spT = nullptr;                    // sparse image: where the fragment of every (row, segment) of S lies (sparse_image.hip)
 	int64_t spT_words = 0;
 	unsigned long long *d_lb_status = nullptr;   // look-back words of the direct sparse output (one per row, then the ticket counters: schur_api.hip)
 	unsigned char *d_scratch = nullptr;   // per-wave dense accumulators (all zero between calls)
 	int64_t scratch_bytes = 0;
 	int64_t scratch_budget = 0;           // 0: up to half of the free HBM; else a cap in bytes
-	int scratch_slots = 0;
-	int64_t slot_bytes = 0, off_bm = 0, off_xn = 0;
-	hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+	hipEvent_t ev[EV_COUNT] = {};
 	int last_rows = 0;
 	int64_t last_nnz = 0;
 };

@@ -1058,6 +1058,28 @@ bool sparse_image_wanted(const spasm_hip_dfact *F, bool other_path_forced, int n
 	const double t_sparse = 8e-6 * (double) S.nlevels + 27e-12 * density * n * Sm + 3e-9 * n + 0.5e-3;
 	return t_sparse < t_other && sparse_image_planned(F, nullptr);
 }
+
+// The rules by which a factor gets the plan of an image, from its sizes alone: what spasm_hip_dfact_create plans by and what
+// the shard decision of spasm_hip_schur predicts BEFORE the factor is planned (r pivots, Sm non-pivotal columns).
+// Sparse image: wide factors, or SPASM_HIP_SPARSE_IMAGE=1 ...
+bool sparse_image_plan_rule(int64_t prime, int r, int Sm)
+{
+	return sparse_image_possible(prime) && r > 0 && Sm > 0 &&
+	       (env_int("SPASM_HIP_SPARSE_IMAGE", -1) == 1 || (Sm >= 8192 && (double) r * (double) Sm >= 5e8));
+}
+
+// ... dense image: when the non-pivotal columns are few enough for dense rows of R (*bytes: what R would take), unless
+// SPASM_HIP_BACKSOLVE=0
+bool dense_image_plan_rule(int64_t prime, int r, int Sm, int64_t nnz, int64_t *bytes)
+{
+	return env_int("SPASM_HIP_BACKSOLVE", -1) != 0 && backsolve_eligible(r, Sm, nnz, bytes, prime);
+}
+
+// Was a row-by-row path asked for by name?  (tests that force a tier or the row-group kernel switch the images off)
+bool row_path_forced()
+{
+	return env_int("SPASM_HIP_FORCE_TIER", 0) != 0 || env_int("SPASM_HIP_GROUP", -1) >= 0;
+}
 }  // namespace sh
 
 extern "C" {
@@ -1599,8 +1621,7 @@ spasm_hip_dfact *spasm_hip_dfact_create(const struct spasm_csr *U, const int *qi
 	// back-substituted image (backsolve.hip): planned when the non-pivotal columns are few enough for dense rows
 	// of R; R itself is computed by the first Schur complement that wants it
 	// sparse image (sparse_image.hip): its dependency tables, for wide factors (R itself is built by the first batch that wants it)
-	const bool plan_sparse = sparse_image_possible(F->prime) && r > 0 && m - r > 0 &&
-	                         (env_int("SPASM_HIP_SPARSE_IMAGE", -1) == 1 || (m - r >= 8192 && (double) r * (double) (m - r) >= 5e8));
+	const bool plan_sparse = sparse_image_plan_rule(F->prime, r, m - r);
 	// (large factors: by a thread of their own, started below once the plan stands where it will stay)
 	const bool plan_sparse_async = plan_sparse && r >= 100000;
 	if (plan_sparse && !plan_sparse_async)
@@ -1609,7 +1630,7 @@ spasm_hip_dfact *spasm_hip_dfact_create(const struct spasm_csr *U, const int *qi
 	if (verbose() >= 2 && F->sp.planned)
 		logmsg("[factor image] tables of the sparse image: %.1f ms\n", 1e3 * (t_bs - t_uploaded));
 	int64_t bs_bytes = 0;
-	if (env_int("SPASM_HIP_BACKSOLVE", -1) != 0 && backsolve_eligible(r, m - r, F->nnz, &bs_bytes, F->prime)) {
+	if (dense_image_plan_rule(F->prime, r, m - r, F->nnz, &bs_bytes)) {
 		if (plan_sparse && env_int("SPASM_HIP_BACKSOLVE", -1) != 1) {
 			// the plan of the dense image waits for a batch that wants it (backsolve_build); what the path choice reads is known now
 			F->bs.r = r;
@@ -1752,7 +1773,7 @@ spasm_hip_dwork *spasm_hip_dwork_create(int max_rows, int m, i64 pool_entries)
 	W->d_blocksum = dalloc<int64_t>((max_rows + 1023) / 1024 + 1);
 	W->d_ctr = dalloc<int>(CTR_COUNT);
 	W->d_ctr64 = dalloc<unsigned long long>(C64_COUNT);
-	for (int e = 0; e < 7; e++)
+	for (int e = 0; e < EV_COUNT; e++)
 		HIP_CHECK(hipEventCreate(&W->ev[e]));
 	return W;
 }
@@ -1761,158 +1782,223 @@ void spasm_hip_dwork_destroy(spasm_hip_dwork *W)
 {
 	if (W == nullptr)
 		return;
-	big_free(W->d_pool_j);
-	big_free(W->d_pool_x);
-	big_free(W->d_Sj);
-	big_free(W->d_Sx);
-	sh::big_free(W->d_row_off);
-	sh::big_free(W->d_row_len);
-	sh::big_free(W->d_ovf1);
-	sh::big_free(W->d_ovf2);
-	sh::big_free(W->d_Sp);
-	sh::big_free(W->d_blocksum);
-	if (W->d_lb_status != nullptr)
-		sh::big_free(W->d_lb_status);
-	if (W->d_stage != nullptr)
-		sh::big_free(W->d_stage);
-	if (W->d_spT != nullptr)
-		sh::big_free(W->d_spT);
-	if (W->d_order != nullptr)
-		sh::big_free(W->d_order);
-	if (W->d_sortbuf != nullptr)
-		sh::big_free(W->d_sortbuf);
-	sh::big_free(W->d_ctr);
-	sh::big_free(W->d_ctr64);
-	sh::big_free(W->d_scratch);
-	for (int e = 0; e < 7; e++)
+	// (the last six grow on demand: NULL when no route asked for them)
+	void *const buffers[] = {W->d_pool_j, W->d_pool_x, W->d_Sj, W->d_Sx, W->d_row_off, W->d_row_len, W->d_ovf1, W->d_ovf2, W->d_Sp, W->d_blocksum, W->d_ctr, W->d_ctr64,
+	                         W->d_lb_status, W->d_stage, W->d_spT, W->d_order, W->d_sortbuf, W->d_scratch};
+	for (void *b : buffers)
+		sh::big_free(b);
+	for (int e = 0; e < EV_COUNT; e++)
 		if (W->ev[e] != nullptr)
 			(void) hipEventDestroy(W->ev[e]);
 	delete W;
 }
 
 // --------------------------------------------------------------------------
-// device Schur complement: three tiers (small LDS table, large LDS table,
-// dense accumulator in HBM), then row pointers + gather/sort.
+// device Schur complement: S = A_n - A_p R from an image of R (sparse or dense) when the factor has one and the batch
+// pays for it, else row by row: the row-group kernel, or three tiers (small LDS table, large LDS table, dense
+// accumulator in HBM); then row pointers + gather/sort unless the route wrote its rows in place.
 // --------------------------------------------------------------------------
 }  // extern "C"
 
 namespace {
-int dschur_impl(const spasm_hip_dcsr *A, const int *d_rows, int nrows, const spasm_hip_dfact *F, spasm_hip_dwork *W,
-                void *stream_, spasm_hip_schur_stats *stats, LOut *Lout)
+// Which way a call goes and with what: decided once per call (choose_route), from the factor, the batch and the environment.
+// The route functions read no switch that is recorded here.
+struct SchurRoute {
+	enum Kind { SPARSE_IMAGE, DENSE_IMAGE, ROW_GROUP, ROW_TIERS } kind = ROW_TIERS;
+	bool in_place = false;            // image routes: rows land in W->d_Sj / d_Sx in their final order, no gather pass from the pool
+	// dense image, direct output: CSR, staged or by look-back is known once R is built (run_dense_image); the settings it hangs on
+	int64_t stage_budget = 0;         // bytes of packed rows the staged output may hold (SPASM_HIP_STAGE_GB, default 8)
+	int64_t stage_rows_forced = 0;    // rows per slice (SPASM_HIP_STAGE_ROWS: tests, slices on small inputs); 0: what the budget holds
+	// row routes
+	int force_tier = 0;               // tests: 1 = start at the large LDS table, 2 = dense accumulators only
+	bool wide_lds = false, wide_dense = false;          // 64-bit sums in the LDS tables / in the dense accumulators
+	int tier_slots = 0;               // per-wave slices of the dense tier and their layout (wave_dense_geometry)
+	i64 tier_slot_bytes = 0, tier_off_bm = 0, tier_off_xn = 0;
+	i64 scratch_need = 0;             // bytes of accumulator scratch the route runs in
+	// row-group kernel
+	bool pull = false;                // left-looking variant (schur_pull.hip) instead of the push kernel
+	bool probe = false;               // auto: the kernel watches its lane efficiency and may give up
+	bool regroup_first = false;       // rows grouped by component of the pivot graph before the launch
+	int waves = 1, slots = 0;
+	i64 slot_bytes = 0, off_bm = 0;
+	long long min_pivots = 0;         // applied pivots before the probe judges
+};
+
+// what a route did to the factor image and how its output went: all the statistics need beyond the route and the counters
+struct SchurOutcome {
+	bool built_sp = false, built_bs = false;          // the sparse image / R was built by this call
+	int staged_slices = 0;            // staged output of the dense image: slices it ran in (0: not used)
+	int csr_tiles = -1;               // CSR output of the dense image: BsDirectOut::csr_tiles of the launch
+};
+
+struct SchurReadback {
+	int ctr[CTR_COUNT];
+	unsigned long long ctr64[C64_COUNT];
+	i64 total = 0;                    // entries of S
+};
+
+const int small_table = 1024, big_table = 8192;
+
+// a workspace buffer of at least `want` elements: kept when it is large enough, else freed and allocated anew (contents undefined)
+template <typename T> void grow(T *&ptr, int64_t &have, int64_t want)
 {
-	hipStream_t stream = (hipStream_t) stream_;
-	const double t_enter = wtime();
-	if (nrows > W->max_rows)
-		die("spasm_hip_dschur: %d rows but the workspace was sized for %d", nrows, W->max_rows);
-	if (A->m != F->m || W->m < F->m)
-		die("spasm_hip_dschur: column count mismatch (A %d, factor %d, workspace %d)", A->m, F->m, W->m);
-	// lazy 32-bit sums in the LDS tables: at most 6144 + 1 terms below p each
-	const bool wide_lds = ((double) F->prime * 6146.0 >= 4294967296.0);
-	// ... and in the dense accumulators: a column receives at most maxdeg + 1 terms, each below 2p (the
-	// row-group kernel adds unreduced products)
-	bool wide_dense = false;          // (set below, once it is known that a row-by-row path runs: it needs the tables of ensure_row_tables)
-	const int small_table = 1024, big_table = 8192;
+	if (have >= want)
+		return;
+	sh::big_free(ptr);
+	ptr = dalloc<T>(want);
+	have = want;
+}
+
+// ... one whose size hangs on the workspace alone (max_rows): allocated on first use
+template <typename T> void grow_once(T *&ptr, int64_t want)
+{
+	if (ptr == nullptr)
+		ptr = dalloc<T>(want);
+}
+
+// The accumulator scratch.  Invariant: it is ALL ZERO between calls, whatever layout the last call gave it (32- or 64-bit sums,
+// per-wave or per-group slices) -- every kernel that runs in it leaves the words it touched at zero, so a buffer that is large
+// enough is taken as it is and only a new one is cleared.
+void grow_scratch(spasm_hip_dwork *W, i64 need, hipStream_t stream)
+{
+	if (need <= W->scratch_bytes)
+		return;
+	sh::big_free(W->d_scratch);
+	HIP_CHECK(sh::malloc_or_trim((void **) &W->d_scratch, (size_t) need));
+	W->scratch_bytes = need;
+	HIP_CHECK(hipMemsetAsync(W->d_scratch, 0, (size_t) need, stream));
+}
+
+// look-back words of the direct output: the status words of the rows, then (on a fresh 128-byte line) the 16 ticket counters,
+// one line each.  Returns the words `nrows` rows use and where the tickets start.
+size_t lookback_words(int nrows, size_t *ticket_at)
+{
+	*ticket_at = ((size_t) nrows + 16) / 16 * 16;
+	return *ticket_at + 16 * 16;
+}
+
+unsigned long long *lookback_buffer(spasm_hip_dwork *W)
+{
+	grow_once(W->d_lb_status, (i64) W->max_rows + 16 + 16 * 16);          // (lookback_words(max_rows), rounded up)
+	return W->d_lb_status;
+}
+
+// Chooses the route of a call.  Everything but the path choice itself (sparse_image_wanted, backsolve_wanted) is here: the
+// switches, the geometry of the accumulator scratch and what the budget makes of it.  The sparse image is built on first use,
+// BEFORE the events of the call start, and a build that finds R dense gives up: the other routes then take the batch -- so
+// the build is part of the choice (*built_sp says whether it happened); the tables of the row routes likewise.
+SchurRoute choose_route(const spasm_hip_dfact *F, const spasm_hip_dwork *W, int nrows, bool records_L, bool *built_sp, hipStream_t stream)
+{
+	SchurRoute R;
 	const int cus = cu_count();
+	// lazy 32-bit sums in the LDS tables: at most 6144 + 1 terms below p each
+	R.wide_lds = ((double) F->prime * 6146.0 >= 4294967296.0);
+	const bool other_forced = sh::row_path_forced();
 	// tests: 1 = start at the large LDS table, 2 = dense accumulators only.  The large table is otherwise
 	// skipped (one wave per CU: slower than the dense tier).
-	int force_tier = env_int("SPASM_HIP_FORCE_TIER", 0);
-	if (Lout != nullptr)
-		force_tier = 2;         // rows must not be restarted once coefficients have been recorded: no LDS tiers
-	const bool use_big = force_tier == 1;
-
+	R.force_tier = env_int("SPASM_HIP_FORCE_TIER", 0);
+	if (records_L)
+		R.force_tier = 2;         // rows must not be restarted once coefficients have been recorded: no LDS tiers
 	// row-group kernel (64 consecutive rows per wave, label-major state) for every row: default for
 	// batches large enough to fill the GPU with groups; SPASM_HIP_GROUP=0/1 forces the choice.
 	// Small batches (density samples, dense blocks) stay on the per-row tiers.
-	int group_mode = env_int("SPASM_HIP_GROUP", -1);
-	bool probe = false;            // auto: run a few groups first and look at their lane efficiency
+	const int group_env = env_int("SPASM_HIP_GROUP", -1);
+	int group_mode = group_env;
 	if (group_mode < 0) {
-		group_mode = (nrows >= 64 * 32 && (force_tier == 0 || Lout != nullptr)) ? 1 : 0;
-		probe = group_mode && Lout == nullptr && nrows >= env_int("SPASM_HIP_GROUP_WATCH_ROWS", 0);
+		group_mode = (nrows >= 64 * 32 && (R.force_tier == 0 || records_L)) ? 1 : 0;
+		// auto: run a few groups first and look at their lane efficiency
+		R.probe = group_mode && !records_L && nrows >= env_int("SPASM_HIP_GROUP_WATCH_ROWS", 0);
 	}
-	int group_slots = 0, group_waves = 1;
-	i64 group_slot_bytes = 0, group_off_bm = 0;
+	// S = A_n - A_p R from the SPARSE image (sparse_image.hip) when the Schur complement is expected to stay sparse
+	bool want_sp = nrows > 0 && !records_L && sparse_image_wanted(F, other_forced, nrows);
+	if (want_sp && !F->sp.valid)
+		want_sp = *built_sp = sparse_image_build(F, stream);
+	if (want_sp) {
+		R.kind = SchurRoute::SPARSE_IMAGE;
+		R.in_place = true;
+		R.probe = false;
+		return R;
+	}
 	// S = A_n - A_p R from the back-substituted image (backsolve.hip) when the factor has one: no accumulator scratch
-	const bool other_forced = env_int("SPASM_HIP_FORCE_TIER", 0) != 0 || env_int("SPASM_HIP_GROUP", -1) >= 0;
-	// S = A_n - A_p R from the SPARSE image (sparse_image.hip) when the Schur complement is expected to stay sparse; the image
-	// is built on first use, and a build that finds R dense gives up: the other paths then take the batch
-	bool want_sp = nrows > 0 && Lout == nullptr && sparse_image_wanted(F, other_forced, nrows);
-	bool built_sp = false;
-	if (want_sp && !F->sp.valid) {
-		built_sp = sparse_image_build(F, stream);
-		want_sp = built_sp;
+	if (nrows > 0 && !records_L && backsolve_wanted(F, other_forced, nrows)) {
+		R.kind = SchurRoute::DENSE_IMAGE;
+		// rows straight into W->d_Sj / d_Sx in their final order (offsets by look-back): no pool, no gather pass
+		R.in_place = env_int("SPASM_HIP_BS_DIRECT", 1) != 0;
+		// packed rows of the staged output: the whole batch when it fits SPASM_HIP_STAGE_GB (default 8), else slices
+		R.stage_budget = (int64_t) env_int("SPASM_HIP_STAGE_GB", 8) << 30;
+		R.stage_rows_forced = std::max(0, env_int("SPASM_HIP_STAGE_ROWS", 0));          // (tests: slices on small inputs)
+		R.probe = false;
+		return R;
 	}
-	const bool want_bs = !want_sp && nrows > 0 && Lout == nullptr && backsolve_wanted(F, other_forced, nrows);
-	if (!want_bs && !want_sp) {
-		// (the components of the pivot graph are what the row-GROUP kernel regroups its rows by: a density sample of 100 rows on the
-		//  per-row tiers only needs the column degrees -- 10 ms of union-find on mk15.b4's factor that nothing ever read)
-		ensure_row_tables(F, stream, group_mode != 0);
-		wide_dense = (2.0 * (double) F->prime * ((double) F->maxdeg + 3.0) >= 4294967296.0);
-	}
+	// (the components of the pivot graph are what the row-GROUP kernel regroups its rows by: a density sample of 100 rows on the
+	//  per-row tiers only needs the column degrees -- 10 ms of union-find on mk15.b4's factor that nothing ever read)
+	ensure_row_tables(F, stream, group_mode != 0);
+	// lazy 32-bit sums in the dense accumulators: a column receives at most maxdeg + 1 terms, each below 2p (the
+	// row-group kernel adds unreduced products)
+	R.wide_dense = (2.0 * (double) F->prime * ((double) F->maxdeg + 3.0) >= 4294967296.0);
 	// per-wave dense scratch, (re)allocated when the factor geometry needs more
-	if (!want_bs && !want_sp) {
-		i64 slot_bytes, off_bm, off_xn;
-		wave_dense_geometry(F->rpad, F->Sm, wide_dense, &slot_bytes, &off_bm, &off_xn);
-		int slots = cus * 32;
-		// accumulator slices may take up to half of the free HBM (288 GB parts: be generous), or what
-		// SPASM_HIP_SCRATCH_GB says
-		size_t free_b = 0, total_b = 0;
-		sh::mem_info(&free_b, &total_b);
-		i64 budget = (i64) ((free_b + (size_t) W->scratch_bytes) / 2);
-		if (W->scratch_budget > 0)
-			budget = std::min(budget, std::max(W->scratch_budget, W->scratch_bytes));
-		if (env_int("SPASM_HIP_SCRATCH_GB", 0) > 0)
-			budget = (i64) env_int("SPASM_HIP_SCRATCH_GB", 0) << 30;
-		slots = (int) std::max<i64>(cus, std::min<i64>(slots, budget / slot_bytes));
-		slots = std::max(1, std::min(slots, nrows));
-		i64 need = slot_bytes * slots;
-		if (group_mode) {
-			group_geometry(F->rpad, F->Sm, wide_dense, &group_slot_bytes, &group_off_bm);
-			const int ngroups = (nrows + 63) / 64;
-			// a slice costs (rpad + Sm) * 256 B (512 B with 64-bit sums): on very wide matrices the budget holds
-			// fewer slices than there are CUs (or none) and the chip would idle -- the per-row tiers need 4 B per
-			// label per wave and run at full occupancy, so they take such batches
-			const i64 slices_that_fit = budget / group_slot_bytes;
-			if (slices_that_fit < 1 || (slices_that_fit < std::min<i64>(ngroups, cus / 2) && env_int("SPASM_HIP_GROUP", -1) < 0)) {
-				group_mode = 0;
-				probe = false;
-			}
+	wave_dense_geometry(F->rpad, F->Sm, R.wide_dense, &R.tier_slot_bytes, &R.tier_off_bm, &R.tier_off_xn);
+	// accumulator slices may take up to half of the free HBM (288 GB parts: be generous), or what
+	// SPASM_HIP_SCRATCH_GB says
+	size_t free_b = 0, total_b = 0;
+	sh::mem_info(&free_b, &total_b);
+	i64 budget = (i64) ((free_b + (size_t) W->scratch_bytes) / 2);
+	if (W->scratch_budget > 0)
+		budget = std::min(budget, std::max(W->scratch_budget, W->scratch_bytes));
+	const int scratch_gb = env_int("SPASM_HIP_SCRATCH_GB", 0);
+	if (scratch_gb > 0)
+		budget = (i64) scratch_gb << 30;
+	R.tier_slots = (int) std::max<i64>(cus, std::min<i64>(cus * 32, budget / R.tier_slot_bytes));
+	R.tier_slots = std::max(1, std::min(R.tier_slots, nrows));
+	R.scratch_need = R.tier_slot_bytes * R.tier_slots;
+	const int ngroups = (nrows + 63) / 64;
+	if (group_mode) {
+		group_geometry(F->rpad, F->Sm, R.wide_dense, &R.slot_bytes, &R.off_bm);
+		// a slice costs (rpad + Sm) * 256 B (512 B with 64-bit sums): on very wide matrices the budget holds
+		// fewer slices than there are CUs (or none) and the chip would idle -- the per-row tiers need 4 B per
+		// label per wave and run at full occupancy, so they take such batches
+		const i64 slices_that_fit = budget / R.slot_bytes;
+		if (slices_that_fit < 1 || (slices_that_fit < std::min<i64>(ngroups, cus / 2) && group_env < 0)) {
+			group_mode = 0;
+			R.probe = false;
 		}
-		if (group_mode) {
-			const int ngroups = (nrows + 63) / 64;
-			// four (two) waves per group while there are at most 3 (12) groups per CU: with few groups the run time is
-			// the chain of level rounds of one group, which the waves split between them (tools/probe_groups.py)
-			// (slots = workgroups = accumulator slices: as many as are resident at two waves per SIMD; the others
-			//  would only wait for a CU and find the queue of groups empty)
-			// ... and the same when it is the BUDGET that keeps the groups in flight few (wide factors: a slice of mk14.b4 is
-			// 80 MB, 297 of them fit the 24 GB of a one-shot call -- one wave each would leave the chip at one wave per CU:
-			// 641 ms against 334 ms with four waves per group)
-			const i64 in_flight = std::min<i64>(ngroups, budget / group_slot_bytes);
-			group_waves = env_int("SPASM_HIP_GROUP_WAVES", in_flight <= cus * 3 ? 4 : in_flight <= cus * 12 ? 2 : 1);
-			group_slots = (int) std::min<i64>((group_waves >= 4 ? cus * 2 : group_waves >= 2 ? cus * 4 : cus * 8),
-			                                  budget / group_slot_bytes);
-			group_slots = std::max(1, std::min(group_slots, ngroups));
-			// with the automatic fallback the per-row tier may run in the same buffer afterwards
-			need = probe ? std::max(need, group_slot_bytes * group_slots) : group_slot_bytes * group_slots;
-		}
-		if (need > W->scratch_bytes) {
-			if (W->d_scratch != nullptr)
-				sh::big_free(W->d_scratch);
-			HIP_CHECK(sh::malloc_or_trim((void **) &W->d_scratch, (size_t) need));
-			W->scratch_bytes = need;
-			HIP_CHECK(hipMemsetAsync(W->d_scratch, 0, (size_t) need, stream));
-		} else if (slot_bytes != W->slot_bytes || off_bm != W->off_bm || off_xn != W->off_xn) {
-			// same buffer, other layout: it is all zero anyway (the kernels restore that invariant)
-		}
-		W->scratch_slots = slots;
-		W->slot_bytes = slot_bytes;
-		W->off_bm = off_bm;
-		W->off_xn = off_xn;
 	}
+	if (!group_mode)
+		return R;
+	R.kind = SchurRoute::ROW_GROUP;
+	// four (two) waves per group while there are at most 3 (12) groups per CU: with few groups the run time is
+	// the chain of level rounds of one group, which the waves split between them (tools/probe_groups.py)
+	// (slots = workgroups = accumulator slices: as many as are resident at two waves per SIMD; the others
+	//  would only wait for a CU and find the queue of groups empty)
+	// ... and the same when it is the BUDGET that keeps the groups in flight few (wide factors: a slice of mk14.b4 is
+	// 80 MB, 297 of them fit the 24 GB of a one-shot call -- one wave each would leave the chip at one wave per CU:
+	// 641 ms against 334 ms with four waves per group)
+	const i64 in_flight = std::min<i64>(ngroups, budget / R.slot_bytes);
+	R.waves = env_int("SPASM_HIP_GROUP_WAVES", in_flight <= cus * 3 ? 4 : in_flight <= cus * 12 ? 2 : 1);
+	R.slots = (int) std::min<i64>((R.waves >= 4 ? cus * 2 : R.waves >= 2 ? cus * 4 : cus * 8), budget / R.slot_bytes);
+	R.slots = std::max(1, std::min(R.slots, ngroups));
+	// with the automatic fallback the per-row tier may run in the same buffer afterwards
+	R.scratch_need = R.probe ? std::max(R.scratch_need, R.slot_bytes * R.slots) : R.slot_bytes * R.slots;
+	// (... per group in flight: the judgement used to fall after 500,000 pivots whatever the number of groups, i.e. after
+	// 1,700 pivots of each of the 297 groups of a mk14.b4 call -- all of them still in the cheap private start of their
+	// rows -- and sent a batch whose final efficiency is 0.60 to the per-row tier: 1.68 s instead of 0.35 s)
+	// (SPASM_HIP_GROUP_MIN_PIVOTS, when set, is the threshold as it stands: tests judge early with it)
+	const char *min_w_env = sh::env_get("SPASM_HIP_GROUP_MIN_PIVOTS");
+	R.min_pivots = (min_w_env != nullptr) ? std::atoll(min_w_env) : std::max<long long>(500000, 8192ll * R.slots);
+	// several connected components in the pivot graph: rows of different components share nothing, so the
+	// rows are grouped by component from the start (the order of the list is kept inside a component; with a
+	// single or a dominant component -- mk13.b5: 109,966 of its 111,177 pivots -- nothing is done)
+	R.regroup_first = env_int("SPASM_HIP_GROUP_REGROUP", 1) != 0 && F->ncomp > 1 && !records_L &&
+	                  (i64) F->comp_largest * 10 < (i64) F->r * 9;          // (a giant component: the list order is what matters)
+	// left-looking numeric pass, no atomics (schur_pull.hip): an experiment; it never gives up
+	R.pull = !records_L && env_int("SPASM_HIP_PULL", 0) != 0 && F->has_pull && pull_lds_bytes(F->rpad, F->Sm) <= (size_t) 150 * 1024;
+	if (R.pull)
+		R.probe = false;
+	return R;
+}
 
-	HIP_CHECK(hipMemsetAsync(W->d_ctr, 0, CTR_COUNT * sizeof(int), stream));
-	HIP_CHECK(hipMemsetAsync(W->d_ctr64, 0, C64_COUNT * sizeof(unsigned long long), stream));
-	HIP_CHECK(hipEventRecord(W->ev[0], stream));
-
+SchurArgs schur_args(const spasm_hip_dcsr *A, const int *d_rows, int nrows, const spasm_hip_dfact *F, const spasm_hip_dwork *W, const LOut *Lout)
+{
 	SchurArgs a{};
 	a.Ap = A->p;
 	a.Aj = A->j;
@@ -1946,338 +2032,329 @@ int dschur_impl(const spasm_hip_dcsr *A, const int *d_rows, int nrows, const spa
 		a.kof = F->d_kof;
 		a.row_orig = Lout->row_orig;
 	}
+	return a;
+}
 
-	bool used_bs = false, built_bs = false, bs_direct = false, use_pull = false;
-	int bs_staged_slices = 0;          // staged output of the back-substituted path: slices it ran in (0: not used)
-	int bs_csr_tiles = -1;             // CSR output of the back-substituted path: BsDirectOut::csr_tiles of the launch
-	if (want_sp) {
-		group_mode = 0;
-		HIP_CHECK(hipEventRecord(W->ev[5], stream));
-		a.list = nullptr;
-		a.list_count = nullptr;
-		a.done_ctr = CTR_DONE2;
-		bs_direct = true;          // rows land in W->d_Sj / d_Sx in their final order: no gather pass from the pool
-		const i64 twords = sparse_image_table_words(nrows, F->sp.nseg);
-		if (W->spT_words < twords) {
-			if (W->d_spT != nullptr)
-				sh::big_free(W->d_spT);
-			W->d_spT = dalloc<uint64_t>(twords);
-			W->spT_words = twords;
-		}
-		if (W->d_lb_status == nullptr)
-			W->d_lb_status = dalloc<unsigned long long>((i64) W->max_rows + 16 + 16 * 16);
-		// the fragments of S go to the row pool of the workspace (4 bytes an entry: pool_cap entries fit pool_j)
-		launch_sparse_image_apply(a, F, reinterpret_cast<uint32_t *>(W->d_pool_j), reinterpret_cast<uint32_t *>(W->d_pool_x), W->pool_cap, W->d_spT, W->d_lb_status, W->d_Sp, W->d_Sj,
-		                          W->d_Sx, W->pool_cap, stream, W->ev[6]);
-		HIP_CHECK(hipEventRecord(W->ev[3], stream));
-		HIP_CHECK(hipEventRecord(W->ev[4], stream));
-		goto eliminated;
+// ---- the routes: each enqueues its kernels and its events on `stream`; EV_CALL_BEGIN and EV_ELIM_END are the driver's ----
+
+void run_sparse_image(SchurArgs a, const spasm_hip_dfact *F, spasm_hip_dwork *W, hipStream_t stream)
+{
+	HIP_CHECK(hipEventRecord(W->ev[EV_PATH_BEGIN], stream));
+	a.done_ctr = CTR_DONE2;
+	grow(W->d_spT, W->spT_words, sparse_image_table_words(a.nrows, F->sp.nseg));
+	// the fragments of S go to the row pool of the workspace (4 bytes an entry: pool_cap entries fit pool_j)
+	launch_sparse_image_apply(a, F, reinterpret_cast<uint32_t *>(W->d_pool_j), reinterpret_cast<uint32_t *>(W->d_pool_x), W->pool_cap, W->d_spT, lookback_buffer(W), W->d_Sp,
+	                          W->d_Sj, W->d_Sx, W->pool_cap, stream, W->ev[EV_APPLY_END]);
+}
+
+void run_dense_image(SchurArgs a, const SchurRoute &route, const spasm_hip_dfact *F, spasm_hip_dwork *W, hipStream_t stream, SchurOutcome &done)
+{
+	// R is built on first use
+	if (!F->bs.valid) {
+		backsolve_build(F, stream);
+		done.built_bs = true;
 	}
-	if (want_bs) {
-		// R is built on first use
-		used_bs = true;
-		group_mode = 0;
-		if (!F->bs.valid) {
-			backsolve_build(F, stream);
-			built_bs = true;
-		}
-		HIP_CHECK(hipEventRecord(W->ev[5], stream));
-		a.list = nullptr;
-		a.list_count = nullptr;
-		a.done_ctr = CTR_DONE2;
-		// rows straight into W->d_Sj / d_Sx in their final order (offsets by look-back): no pool, no gather pass
-		bs_direct = env_int("SPASM_HIP_BS_DIRECT", 1) != 0;
-		if (bs_direct) {
-			if (W->d_lb_status == nullptr)
-				W->d_lb_status = dalloc<unsigned long long>((i64) W->max_rows + 16 + 16 * 16);
-			// status words of the rows, then (on a fresh 128-byte line) the 16 ticket counters, one line each
-			const size_t ticket_at = ((size_t) nrows + 16) / 16 * 16;
-			HIP_CHECK(hipMemsetAsync(W->d_lb_status, 0, (ticket_at + 16 * 16) * sizeof(unsigned long long), stream));
-			BsDirectOut out{W->d_lb_status, reinterpret_cast<int *>(W->d_lb_status + ticket_at), W->d_Sp, W->d_Sj, W->d_Sx, W->pool_cap};
-			int64_t stage_row_bytes = 0;
-			if (backsolve_stages_output(F, &stage_row_bytes) && nrows > 0) {
-				// packed rows of the staged output: the whole batch when it fits SPASM_HIP_STAGE_GB (default 8), else slices
-				const int64_t budget = (int64_t) env_int("SPASM_HIP_STAGE_GB", 8) << 30;
-				int64_t rows_fit = std::max<int64_t>(1024, budget / stage_row_bytes);
-				if (env_int("SPASM_HIP_STAGE_ROWS", 0) > 0)          // (tests: slices on small inputs)
-					rows_fit = env_int("SPASM_HIP_STAGE_ROWS", 0);
-				out.stage_rows = std::min<int64_t>(nrows, rows_fit);
-				if (backsolve_output_csr(F, nrows, out.stage_rows)) {
-					out.csr = true;          // every row of S from the apply kernel straight to its place: no staging buffer
-				} else {
-					const int64_t need = out.stage_rows * stage_row_bytes;
-					if (W->stage_bytes < need) {
-						if (W->d_stage != nullptr)
-							sh::big_free(W->d_stage);
-						W->d_stage = dalloc<uint32_t>(need / 4);
-						W->stage_bytes = need;
-					}
-					out.stage = W->d_stage;
-					out.ev_expand = W->ev[6];
-				}
-			}
-			launch_backsolve_apply(a, F, nullptr, 0, stream, &out);
-			bs_staged_slices = out.staged ? out.slices : 0;
-			bs_csr_tiles = out.csr_tiles;
+	HIP_CHECK(hipEventRecord(W->ev[EV_PATH_BEGIN], stream));
+	a.done_ctr = CTR_DONE2;
+	if (!route.in_place) {
+		launch_backsolve_apply(a, F, nullptr, 0, stream, nullptr);          // rows to the pool: the gather pass follows
+		return;
+	}
+	size_t ticket_at = 0;
+	const size_t words = lookback_words(a.nrows, &ticket_at);
+	unsigned long long *lb = lookback_buffer(W);
+	HIP_CHECK(hipMemsetAsync(lb, 0, words * sizeof(unsigned long long), stream));
+	BsDirectOut out{lb, reinterpret_cast<int *>(lb + ticket_at), W->d_Sp, W->d_Sj, W->d_Sx, W->pool_cap};
+	int64_t stage_row_bytes = 0;
+	if (backsolve_stages_output(F, &stage_row_bytes) && a.nrows > 0) {
+		const int64_t rows_fit = (route.stage_rows_forced > 0) ? route.stage_rows_forced : std::max<int64_t>(1024, route.stage_budget / stage_row_bytes);
+		out.stage_rows = std::min<int64_t>(a.nrows, rows_fit);
+		if (backsolve_output_csr(F, a.nrows, out.stage_rows)) {
+			out.csr = true;          // every row of S from the apply kernel straight to its place: no staging buffer
 		} else {
-			launch_backsolve_apply(a, F, nullptr, 0, stream, nullptr);
+			grow(W->d_stage, W->stage_words, out.stage_rows * stage_row_bytes / 4);
+			out.stage = W->d_stage;
+			out.ev_expand = W->ev[EV_EXPAND_BEGIN];
 		}
-		HIP_CHECK(hipEventRecord(W->ev[3], stream));
-		HIP_CHECK(hipEventRecord(W->ev[4], stream));
-		goto eliminated;
 	}
-	if (nrows > 0) {
-		// tier 0: small LDS table, many waves per CU
-		a.list = nullptr;
-		a.list_count = nullptr;
-		a.ovf_list = W->d_ovf1;
-		a.next_ctr = CTR_ROW_NEXT;
-		a.ovf_ctr = CTR_OVF1;
-		a.done_ctr = CTR_DONE0;
-		const int per_cu0 = (int) std::min<size_t>(16, (size_t) (160 * 1024) / schur_lds_bytes(small_table, wide_lds));
-		int blocks0 = std::min(cus * per_cu0, (nrows + 3) / 4);
-		if (group_mode) {
-			a.next_ctr = CTR_ROW_NEXT_G;
-			a.done_ctr = CTR_DONE2;
-			// auto mode: the kernel watches its own lane efficiency (eliminations / (64 * applied pivots)).
-			// The break-even against the per-row kernel is near 0.15 (one coalesced atomic instruction per
-			// pivot entry at 2.6 G/s against one scattered update per row at 23 G/s),
-			// but the efficiency of a healthy batch starts low (the first eliminations of a row are its
-			// own, the shared part of the reach comes later: mk13.b5 is under 0.15 for its first 10 ms),
-			// so the kernel only bails out of hopeless batches: under 0.04 after 500,000 applied pivots.
-			// Abandoned rows keep row_len == -1 and go to the per-row tiers.
-			HIP_CHECK(hipMemsetAsync(W->d_row_len, 0xFF, (size_t) nrows * sizeof(int), stream));
-			const float min_eff = (float) (4) / 100.0f;
-			// (... per group in flight: the judgement used to fall after 500,000 pivots whatever the number of groups, i.e. after
-			// 1,700 pivots of each of the 297 groups of a mk14.b4 call -- all of them still in the cheap private start of their
-			// rows -- and sent a batch whose final efficiency is 0.60 to the per-row tier: 1.68 s instead of 0.35 s)
-			// (SPASM_HIP_GROUP_MIN_PIVOTS, when set, is the threshold as it stands: tests judge early with it)
-			const char *min_w_env = sh::env_get("SPASM_HIP_GROUP_MIN_PIVOTS");
-			const long long min_w = (min_w_env != nullptr) ? std::atoll(min_w_env) : std::max<long long>(500000, 8192ll * group_slots);
-			// several connected components in the pivot graph: rows of different components share nothing, so the
-			// rows are grouped by component from the start (the order of the list is kept inside a component; with a
-			// single or a dominant component -- mk13.b5: 109,966 of its 111,177 pivots -- nothing is done)
-			const bool regroup_enabled = env_int("SPASM_HIP_GROUP_REGROUP", 1) != 0;
-			auto regroup = [&]() {
-				const int64_t need = regroup_scratch_ints(nrows, F->rpad);
-				if (W->sortbuf_ints < need) {
-					if (W->d_sortbuf != nullptr)
-						sh::big_free(W->d_sortbuf);
-					W->d_sortbuf = dalloc<int>(need);
-					W->sortbuf_ints = need;
-				}
-				if (W->d_order == nullptr)
-					W->d_order = dalloc<int>(W->max_rows);
-				launch_regroup_rows(a, W->d_sortbuf, W->d_order, stream);
-			};
-			const bool grouped_first = regroup_enabled && F->ncomp > 1 && Lout == nullptr &&
-			                           (i64) F->comp_largest * 10 < (i64) F->r * 9;          // (a giant component: the list order is what matters)
-			if (grouped_first) {
-				regroup();
-				a.order = W->d_order;
-			}
-			use_pull = Lout == nullptr && env_int("SPASM_HIP_PULL", 0) != 0 && F->has_pull && pull_lds_bytes(F->rpad, F->Sm) <= (size_t) 150 * 1024;
-			if (use_pull) {
-				// left-looking numeric pass, no atomics (schur_pull.hip); its slices are the row-group kernel's without the bitmap
-				const int per_cu = (int) std::max<size_t>(1, std::min<size_t>(8, (size_t) (160 * 1024) / (pull_lds_bytes(F->rpad, F->Sm) + 5 * 1024)));
-				const int pull_slots = (int) std::max<i64>(1, std::min<i64>(std::min<i64>((nrows + 63) / 64, (i64) cus * per_cu),
-				                                                          W->scratch_bytes / pull_slot_bytes(F->rpad, F->Sm)));
-				probe = false;
-				launch_schur_pull(a, W->d_scratch, pull_slot_bytes(F->rpad, F->Sm), F->d_cp, F->d_cent, F->d_lvl, F->nlevels, pull_slots, stream);
-			} else
-			launch_schur_group(a, W->d_scratch, group_slot_bytes, group_off_bm, wide_dense, nullptr, 0, group_slots, stream,
-			                   probe ? 1 : 0, min_eff, min_w, group_waves);
-			a.order = nullptr;
-			a.skip_ctr = CTR_GROUP_ABORT;
-			// did it give up?  (one small read-back: the call blocks at its end anyway, and nothing is launched
-			// for nothing -- the kernels below also check the flags themselves)
-			int gave_up = 0;
-			if (probe) {
-				HIP_CHECK(hipMemcpyAsync(&gave_up, W->d_ctr + CTR_GROUP_ABORT, sizeof(int), hipMemcpyDeviceToHost, stream));
-				HIP_CHECK(hipStreamSynchronize(stream));
-			}
-			HIP_CHECK(hipEventRecord(W->ev[5], stream));
-			if (!probe || !gave_up) {
-				HIP_CHECK(hipEventRecord(W->ev[3], stream));
-				HIP_CHECK(hipEventRecord(W->ev[4], stream));
-				goto eliminated;
-			}
-			a.skip_done = 1;
-			a.next_ctr = CTR_ROW_NEXT;
-			a.done_ctr = CTR_DONE0;
-		}
-		if (force_tier == 0)
-			launch_schur_lds(a, small_table, wide_lds, std::max(blocks0, 1), stream);
-		else
-			launch_all_rows_to_list(W->d_ovf1, W->d_ctr + CTR_OVF1, W->d_row_len, nrows, stream);
-		HIP_CHECK(hipEventRecord(W->ev[3], stream));
-		// tier 1 (optional): large LDS table, one wave per CU
-		const int *last_list = W->d_ovf1;
-		const int *last_count = W->d_ctr + CTR_OVF1;
-		if (use_big) {
-			a.list = W->d_ovf1;
-			a.list_count = W->d_ctr + CTR_OVF1;
-			a.ovf_list = W->d_ovf2;
-			a.next_ctr = CTR_ROW_NEXT2;
-			a.ovf_ctr = CTR_OVF2;
-			a.done_ctr = CTR_DONE1;
-			launch_schur_lds(a, big_table, wide_lds, cus, stream);
-			last_list = W->d_ovf2;
-			last_count = W->d_ctr + CTR_OVF2;
-		}
-		HIP_CHECK(hipEventRecord(W->ev[4], stream));
-		// tier 2: dense accumulators in HBM, one wave per row, thousands of rows in flight
-		a.list = last_list;
-		a.list_count = last_count;
-		a.ovf_list = nullptr;
-		a.next_ctr = CTR_ROW_NEXT3;
-		a.ovf_ctr = CTR_OVF2;
-		a.done_ctr = CTR_DONE2;
-		launch_schur_wave_dense(a, W->d_scratch, W->slot_bytes, W->off_bm, W->off_xn, wide_dense, nullptr, 0,
-		                        W->scratch_slots, stream);
-	}
-eliminated:
-	HIP_CHECK(hipEventRecord(W->ev[1], stream));
-	if (!bs_direct)
-		launch_finalize(W, nrows, stream);
-	HIP_CHECK(hipEventRecord(W->ev[2], stream));
+	launch_backsolve_apply(a, F, nullptr, 0, stream, &out);
+	done.staged_slices = out.staged ? out.slices : 0;
+	done.csr_tiles = out.csr_tiles;
+}
 
-	int ctr[CTR_COUNT];
-	unsigned long long ctr64[C64_COUNT];
-	i64 total = 0;
-	HIP_CHECK(hipMemcpyAsync(ctr, W->d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, stream));
-	HIP_CHECK(hipMemcpyAsync(ctr64, W->d_ctr64, sizeof(ctr64), hipMemcpyDeviceToHost, stream));
-	HIP_CHECK(hipMemcpyAsync(&total, W->d_Sp + nrows, sizeof(i64), hipMemcpyDeviceToHost, stream));
+// The row-group kernel (push or pull) on every row.  Returns whether it gave up (only with route.probe): the rows it
+// abandoned keep row_len == -1 and go to the per-row tiers (run_row_tiers with skip_done).
+bool run_row_group(SchurArgs a, const SchurRoute &route, const spasm_hip_dfact *F, spasm_hip_dwork *W, hipStream_t stream)
+{
+	a.next_ctr = CTR_ROW_NEXT_G;
+	a.done_ctr = CTR_DONE2;
+	HIP_CHECK(hipMemsetAsync(W->d_row_len, 0xFF, (size_t) a.nrows * sizeof(int), stream));
+	if (route.regroup_first) {
+		grow(W->d_sortbuf, W->sortbuf_ints, regroup_scratch_ints(a.nrows, F->rpad));
+		grow_once(W->d_order, (i64) W->max_rows);
+		launch_regroup_rows(a, W->d_sortbuf, W->d_order, stream);
+		a.order = W->d_order;
+	}
+	if (route.pull) {
+		// its slices are the row-group kernel's without the bitmap
+		const int per_cu = (int) std::max<size_t>(1, std::min<size_t>(8, (size_t) (160 * 1024) / (pull_lds_bytes(F->rpad, F->Sm) + 5 * 1024)));
+		const int pull_slots = (int) std::max<i64>(1, std::min<i64>(std::min<i64>((a.nrows + 63) / 64, (i64) cu_count() * per_cu),
+		                                                          W->scratch_bytes / pull_slot_bytes(F->rpad, F->Sm)));
+		launch_schur_pull(a, W->d_scratch, pull_slot_bytes(F->rpad, F->Sm), F->d_cp, F->d_cent, F->d_lvl, F->nlevels, pull_slots, stream);
+	} else {
+		// auto mode: the kernel watches its own lane efficiency (eliminations / (64 * applied pivots)).
+		// The break-even against the per-row kernel is near 0.15 (one coalesced atomic instruction per
+		// pivot entry at 2.6 G/s against one scattered update per row at 23 G/s),
+		// but the efficiency of a healthy batch starts low (the first eliminations of a row are its
+		// own, the shared part of the reach comes later: mk13.b5 is under 0.15 for its first 10 ms),
+		// so the kernel only bails out of hopeless batches: under 0.04 after route.min_pivots applied pivots.
+		const float min_eff = (float) (4) / 100.0f;
+		launch_schur_group(a, W->d_scratch, route.slot_bytes, route.off_bm, route.wide_dense, nullptr, 0, route.slots, stream, route.probe ? 1 : 0, min_eff,
+		                   route.min_pivots, route.waves);
+	}
+	// did it give up?  (one small read-back: the call blocks at its end anyway, and nothing is launched
+	// for nothing -- the per-row kernels also check the flags themselves)
+	int gave_up = 0;
+	if (route.probe) {
+		HIP_CHECK(hipMemcpyAsync(&gave_up, W->d_ctr + CTR_GROUP_ABORT, sizeof(int), hipMemcpyDeviceToHost, stream));
+		HIP_CHECK(hipStreamSynchronize(stream));
+	}
+	HIP_CHECK(hipEventRecord(W->ev[EV_GROUP_END], stream));
+	if (gave_up)
+		return true;
+	HIP_CHECK(hipEventRecord(W->ev[EV_TIER0_END], stream));
+	HIP_CHECK(hipEventRecord(W->ev[EV_TIER1_END], stream));
+	return false;
+}
+
+// The per-row tiers; skip_done: after a row-group kernel that gave up, only the rows it left (row_len == -1).
+void run_row_tiers(SchurArgs a, const SchurRoute &route, spasm_hip_dwork *W, hipStream_t stream, bool skip_done)
+{
+	const int cus = cu_count();
+	if (skip_done) {
+		a.skip_ctr = CTR_GROUP_ABORT;
+		a.skip_done = 1;
+	}
+	// tier 0: small LDS table, many waves per CU
+	a.ovf_list = W->d_ovf1;
+	a.next_ctr = CTR_ROW_NEXT;
+	a.ovf_ctr = CTR_OVF1;
+	a.done_ctr = CTR_DONE0;
+	const int per_cu0 = (int) std::min<size_t>(16, (size_t) (160 * 1024) / schur_lds_bytes(small_table, route.wide_lds));
+	const int blocks0 = std::min(cus * per_cu0, (a.nrows + 3) / 4);
+	if (route.force_tier == 0)
+		launch_schur_lds(a, small_table, route.wide_lds, std::max(blocks0, 1), stream);
+	else
+		launch_all_rows_to_list(W->d_ovf1, W->d_ctr + CTR_OVF1, W->d_row_len, a.nrows, stream);
+	HIP_CHECK(hipEventRecord(W->ev[EV_TIER0_END], stream));
+	// tier 1 (optional): large LDS table, one wave per CU
+	const bool use_big = route.force_tier == 1;
+	if (use_big) {
+		a.list = W->d_ovf1;
+		a.list_count = W->d_ctr + CTR_OVF1;
+		a.ovf_list = W->d_ovf2;
+		a.next_ctr = CTR_ROW_NEXT2;
+		a.ovf_ctr = CTR_OVF2;
+		a.done_ctr = CTR_DONE1;
+		launch_schur_lds(a, big_table, route.wide_lds, cus, stream);
+	}
+	HIP_CHECK(hipEventRecord(W->ev[EV_TIER1_END], stream));
+	// tier 2: dense accumulators in HBM, one wave per row, thousands of rows in flight
+	a.list = use_big ? W->d_ovf2 : W->d_ovf1;
+	a.list_count = W->d_ctr + (use_big ? CTR_OVF2 : CTR_OVF1);
+	a.ovf_list = nullptr;
+	a.next_ctr = CTR_ROW_NEXT3;
+	a.ovf_ctr = CTR_OVF2;
+	a.done_ctr = CTR_DONE2;
+	launch_schur_wave_dense(a, W->d_scratch, route.tier_slot_bytes, route.tier_off_bm, route.tier_off_xn, route.wide_dense, nullptr, 0, route.tier_slots, stream);
+}
+
+// ---- statistics: zero, the common counters, then what the route of the call has to say ----
+
+void sparse_image_stats(spasm_hip_schur_stats *stats, const SchurOutcome &done, const spasm_hip_dfact *F, const spasm_hip_dwork *W, int nrows, const SchurReadback &rb)
+{
+	const SpImage &P = F->sp;
+	const i64 total = rb.total;
+	if (done.built_sp)
+		HIP_CHECK(hipEventElapsedTime(&stats->ms_sparse_build, P.ev0, P.ev1));
+	HIP_CHECK(hipEventElapsedTime(&stats->ms_sparse_apply, W->ev[EV_PATH_BEGIN], W->ev[EV_APPLY_END]));
+	HIP_CHECK(hipEventElapsedTime(&stats->ms_sparse_gather, W->ev[EV_APPLY_END], W->ev[EV_ELIM_END]));
+	stats->sparse_image_nnz = P.nnz;
+	stats->sparse_image_ops_build = P.ops_build;
+	stats->sparse_image_ops_apply = (i64) rb.ctr64[C64_STREAM];
+	stats->sparse_image_levels = P.nlevels;
+	stats->sparse_image_launches = P.launches;
+	// algorithmic bytes.  Build: every fragment entry read once per row that uses it and written
+	// once (4 B each), the fragment words (8 B per dependency and segment + 8 B per row and segment), the entries of U'.
+	// Rows of S: the fragment entries read (4 B), a fragment word per pivotal entry and segment, the entries in and the
+	// fragments of S out (4 B); gather: fragments in (4 B), pairs out (8 B), 8 B per (row, segment).
+	stats->bytes_sparse_build = 4 * (P.ops_build + P.nnz) + 8 * (P.ndeps + (i64) P.r) * P.nseg + 8 * F->nnz;
+	stats->bytes_sparse_apply = 4 * (i64) rb.ctr64[C64_STREAM] + 8 * (i64) rb.ctr64[C64_ELIM] * P.nseg + 8 * (i64) rb.ctr64[C64_INPUT] + 4 * total +
+	                            8 * (i64) nrows * P.nseg;
+	stats->bytes_sparse_gather = 12 * total + 8 * (i64) nrows * P.nseg + 8 * (i64) nrows;
+	const bool build_dominates = stats->ms_sparse_build > stats->ms_sparse_apply;
+	snprintf(stats->kernel, sizeof(stats->kernel), "%s", build_dominates ? "sp_build_kernel" : "sp_apply_kernel");
+	snprintf(stats->kernel_other, sizeof(stats->kernel_other), "%s", build_dominates ? "sp_apply_kernel" : "sp_build_kernel");
+	snprintf(stats->kernel_expand, sizeof(stats->kernel_expand), "sp_gather_kernel");
+}
+
+void dense_image_stats(spasm_hip_schur_stats *stats, const SchurOutcome &done, const spasm_hip_dfact *F, const spasm_hip_dwork *W, int nrows, const SchurReadback &rb)
+{
+	const BsImage &B = F->bs;
+	const i64 total = rb.total;
+	if (done.built_bs) {
+		HIP_CHECK(hipEventElapsedTime(&stats->ms_backsolve, B.ev0, B.ev1));
+		// every row of R written once and read once per dependency; the entries of U' read once
+		stats->bytes_backsolve = ((i64) B.r + B.ndeps) * (i64) B.Sm * B.elem_bytes + 8 * F->nnz;
+	}
+	HIP_CHECK(hipEventElapsedTime(&stats->ms_apply, W->ev[EV_PATH_BEGIN], W->ev[EV_ELIM_END]));
+	// one row of R per pivotal entry of the reduced rows, the entries in and out, 20 B per row
+	stats->bytes_apply = (i64) rb.ctr64[C64_ELIM] * (i64) B.Sm * B.elem_bytes + 8 * ((i64) rb.ctr64[C64_INPUT] + total) + 20 * (i64) nrows;
+	if (done.staged_slices > 0) {
+		// staged output: the entries of S leave through bs_expand_s16_kernel; with one slice the two kernels are timed apart
+		stats->bytes_apply -= 8 * total;
+		stats->bytes_expand = 8 * total;
+		stats->bytes_staged = (i64) nrows * B.ldR * B.elem_bytes;
+		snprintf(stats->kernel_expand, sizeof(stats->kernel_expand), "bs_expand_kernel<%d>", B.sgn ? 0 : B.elem_bytes == 2 ? 1 : 2);
+		if (done.staged_slices == 1) {
+			HIP_CHECK(hipEventElapsedTime(&stats->ms_apply, W->ev[EV_PATH_BEGIN], W->ev[EV_EXPAND_BEGIN]));
+			HIP_CHECK(hipEventElapsedTime(&stats->ms_expand, W->ev[EV_EXPAND_BEGIN], W->ev[EV_ELIM_END]));
+		}
+	}
+	char apply_name[32];
+	if (B.sgn && done.csr_tiles == 0)          // (the CSR output's two-buffer kernel: wide rows, A/B runs)
+		snprintf(apply_name, sizeof(apply_name), "bs_apply_s16_kernel<lds2>");
+	else if (B.sgn)
+		snprintf(apply_name, sizeof(apply_name), "bs_apply_s16_kernel");
+	else
+		snprintf(apply_name, sizeof(apply_name), "bs_apply_kernel<%s,%s>", B.elem_bytes == 2 ? "true" : "false", B.plain ? "true" : "false");
+	const bool build_dominates = stats->ms_backsolve > stats->ms_apply;
+	snprintf(stats->kernel, sizeof(stats->kernel), "%s", build_dominates ? B.kernel_build : apply_name);
+	snprintf(stats->kernel_other, sizeof(stats->kernel_other), "%s", build_dominates ? apply_name : B.kernel_build);
+}
+
+void row_route_stats(spasm_hip_schur_stats *stats, const SchurRoute &route, const spasm_hip_dfact *F, const spasm_hip_dwork *W, int nrows)
+{
+	const bool group = route.kind == SchurRoute::ROW_GROUP;
+	if (group) {
+		stats->used_group_kernel = 1;
+		stats->group_slots = route.slots;
+		stats->group_waves = route.waves;
+		stats->group_slot_bytes = route.slot_bytes;
+		stats->group_slots_wanted = (int) std::min<i64>((nrows + 63) / 64, (i64) cu_count() * 8 / std::max(1, route.waves));
+	}
+	if (group && route.pull)
+		snprintf(stats->kernel, sizeof(stats->kernel), "schur_pull_kernel");
+	else if (group && !stats->group_aborted)
+		schur_group_variant_name(F->rpad, route.wide_dense, route.waves, stats->kernel, sizeof(stats->kernel));
+	else
+		snprintf(stats->kernel, sizeof(stats->kernel), "schur_wave_dense_kernel<%s>", route.wide_dense ? "true" : "false");
+	if (nrows == 0)
+		return;          // (nothing was launched and no event but the driver's recorded)
+	if (group)
+		HIP_CHECK(hipEventElapsedTime(&stats->ms_group, W->ev[EV_CALL_BEGIN], W->ev[EV_GROUP_END]));
+	HIP_CHECK(hipEventElapsedTime(&stats->ms_tier0, W->ev[group ? EV_GROUP_END : EV_CALL_BEGIN], W->ev[EV_TIER0_END]));
+	HIP_CHECK(hipEventElapsedTime(&stats->ms_tier1, W->ev[EV_TIER0_END], W->ev[EV_TIER1_END]));
+	HIP_CHECK(hipEventElapsedTime(&stats->ms_tier2, W->ev[EV_TIER1_END], W->ev[EV_ELIM_END]));
+}
+
+void write_stats(spasm_hip_schur_stats *stats, const SchurRoute &route, const SchurOutcome &done, const spasm_hip_dfact *F, const spasm_hip_dwork *W, int nrows,
+                 const SchurReadback &rb)
+{
+	*stats = spasm_hip_schur_stats{};
+	stats->nnz = rb.total;
+	stats->eliminations = (i64) rb.ctr64[C64_ELIM];
+	stats->entries_streamed = (i64) rb.ctr64[C64_STREAM];
+	stats->input_entries = (i64) rb.ctr64[C64_INPUT];
+	stats->group_pivots = (i64) rb.ctr64[C64_WAVEPIV];
+	stats->rows = nrows;
+	stats->rows_lds = rb.ctr[CTR_DONE0];
+	stats->rows_lds_big = rb.ctr[CTR_DONE1];
+	stats->rows_dense = rb.ctr[CTR_DONE2];          // (the rows of the image routes and of the row-group kernel are counted here too)
+	stats->status = rb.ctr[CTR_STATUS] & 3;
+	stats->group_aborted = rb.ctr[CTR_GROUP_ABORT] ? 1 : 0;
+	stats->used_sparse_image = route.kind == SchurRoute::SPARSE_IMAGE;
+	stats->sparse_image_built = done.built_sp;
+	stats->used_backsolve = route.kind == SchurRoute::DENSE_IMAGE;
+	stats->backsolve_built = done.built_bs;
+	HIP_CHECK(hipEventElapsedTime(&stats->ms_eliminate, W->ev[EV_CALL_BEGIN], W->ev[EV_ELIM_END]));
+	HIP_CHECK(hipEventElapsedTime(&stats->ms_finalize, W->ev[EV_ELIM_END], W->ev[EV_FINALIZE_END]));
+	HIP_CHECK(hipEventElapsedTime(&stats->ms_total, W->ev[EV_CALL_BEGIN], W->ev[EV_FINALIZE_END]));
+	switch (route.kind) {
+	case SchurRoute::SPARSE_IMAGE:
+		sparse_image_stats(stats, done, F, W, nrows, rb);
+		break;
+	case SchurRoute::DENSE_IMAGE:
+		dense_image_stats(stats, done, F, W, nrows, rb);
+		break;
+	case SchurRoute::ROW_GROUP:
+	case SchurRoute::ROW_TIERS:
+		row_route_stats(stats, route, F, W, nrows);
+		break;
+	}
+	if (done.built_sp) {          // (the sparse image is built before the events of the call start: its time belongs to the call)
+		stats->ms_total += stats->ms_sparse_build;
+		stats->ms_eliminate += stats->ms_sparse_build;
+	}
+}
+
+int dschur_impl(const spasm_hip_dcsr *A, const int *d_rows, int nrows, const spasm_hip_dfact *F, spasm_hip_dwork *W,
+                void *stream_, spasm_hip_schur_stats *stats, LOut *Lout)
+{
+	hipStream_t stream = (hipStream_t) stream_;
+	const double t_enter = wtime();
+	if (nrows > W->max_rows)
+		die("spasm_hip_dschur: %d rows but the workspace was sized for %d", nrows, W->max_rows);
+	if (A->m != F->m || W->m < F->m)
+		die("spasm_hip_dschur: column count mismatch (A %d, factor %d, workspace %d)", A->m, F->m, W->m);
+	SchurOutcome done;
+	const SchurRoute route = choose_route(F, W, nrows, Lout != nullptr, &done.built_sp, stream);
+	grow_scratch(W, route.scratch_need, stream);
+
+	HIP_CHECK(hipMemsetAsync(W->d_ctr, 0, CTR_COUNT * sizeof(int), stream));
+	HIP_CHECK(hipMemsetAsync(W->d_ctr64, 0, C64_COUNT * sizeof(unsigned long long), stream));
+	HIP_CHECK(hipEventRecord(W->ev[EV_CALL_BEGIN], stream));
+	const SchurArgs a = schur_args(A, d_rows, nrows, F, W, Lout);
+	if (route.kind == SchurRoute::SPARSE_IMAGE) {
+		run_sparse_image(a, F, W, stream);
+	} else if (route.kind == SchurRoute::DENSE_IMAGE) {
+		run_dense_image(a, route, F, W, stream, done);
+	} else if (nrows > 0) {
+		const bool gave_up = route.kind == SchurRoute::ROW_GROUP && run_row_group(a, route, F, W, stream);
+		if (route.kind == SchurRoute::ROW_TIERS || gave_up)
+			run_row_tiers(a, route, W, stream, /* skip_done = */ gave_up);
+	}
+	HIP_CHECK(hipEventRecord(W->ev[EV_ELIM_END], stream));
+	if (!route.in_place)
+		launch_finalize(W, nrows, stream);
+	HIP_CHECK(hipEventRecord(W->ev[EV_FINALIZE_END], stream));
+
+	SchurReadback rb;
+	HIP_CHECK(hipMemcpyAsync(rb.ctr, W->d_ctr, sizeof(rb.ctr), hipMemcpyDeviceToHost, stream));
+	HIP_CHECK(hipMemcpyAsync(rb.ctr64, W->d_ctr64, sizeof(rb.ctr64), hipMemcpyDeviceToHost, stream));
+	HIP_CHECK(hipMemcpyAsync(&rb.total, W->d_Sp + nrows, sizeof(i64), hipMemcpyDeviceToHost, stream));
 	const double t_enqueued = wtime();
 	HIP_CHECK(hipStreamSynchronize(stream));
 	if (verbose() >= 3)
 		logmsg("[schur/hip] %d rows: %.2f ms of host work up to the last launch, %.2f ms waiting for the device\n", nrows, 1e3 * (t_enqueued - t_enter),
 		       1e3 * (wtime() - t_enqueued));
 	W->last_rows = nrows;
-	W->last_nnz = total;
-	if (ctr[CTR_STATUS] & 4)
+	W->last_nnz = rb.total;
+	if (rb.ctr[CTR_STATUS] & 4)
 		die("spasm_hip_dschur: a row waited for its predecessors' lengths for too long (look-back of the direct output)");
-	const int status = ctr[CTR_STATUS] & 3;      // bit 0: row pool exhausted, bit 1: L pool exhausted
 #ifdef SPASM_GROUP_PROFILE
-	if (group_mode) {
+	if (route.kind == SchurRoute::ROW_GROUP) {
 		static const char *const phase[8] = {"drain", "watch", "bitmap scan", "level end", "gather pending", "apply+scatter", "output count", "output write"};
 		const double g = (double) ((nrows + 63) / 64);
 		for (int q = 0; q < 8; q++)
-			fprintf(stderr, "[spasm_hip profile] %-15s %12.0f per group\n", phase[q], (double) ctr64[C64_PROF0 + q] / g);
+			fprintf(stderr, "[spasm_hip profile] %-15s %12.0f per group\n", phase[q], (double) rb.ctr64[C64_PROF0 + q] / g);
 	}
 #endif
 	if (Lout != nullptr)
-		Lout->used = (i64) ctr64[C64_LPOOL];
-	if (stats != nullptr) {
-		stats->nnz = total;
-		stats->eliminations = (i64) ctr64[C64_ELIM];
-		stats->entries_streamed = (i64) ctr64[C64_STREAM];
-		stats->input_entries = (i64) ctr64[C64_INPUT];
-		stats->group_pivots = (i64) ctr64[C64_WAVEPIV];
-		stats->used_group_kernel = group_mode ? 1 : 0;
-		stats->group_slots = group_mode ? group_slots : 0;
-		stats->group_waves = group_mode ? group_waves : 0;
-		stats->group_slot_bytes = group_mode ? group_slot_bytes : 0;
-		stats->group_slots_wanted = group_mode ? (int) std::min<i64>((nrows + 63) / 64, (i64) cus * 8 / std::max(1, group_waves)) : 0;
-		stats->rows = nrows;
-		stats->rows_lds = ctr[CTR_DONE0];
-		stats->rows_lds_big = ctr[CTR_DONE1];
-		stats->rows_dense = ctr[CTR_DONE2];
-		stats->status = status;
-		HIP_CHECK(hipEventElapsedTime(&stats->ms_eliminate, W->ev[0], W->ev[1]));
-		stats->ms_tier0 = stats->ms_tier1 = stats->ms_tier2 = stats->ms_group = 0.0f;
-		stats->group_aborted = ctr[CTR_GROUP_ABORT] ? 1 : 0;
-		stats->used_backsolve = used_bs ? 1 : 0;
-		stats->backsolve_built = built_bs ? 1 : 0;
-		stats->ms_backsolve = stats->ms_apply = 0.0f;
-		stats->bytes_backsolve = stats->bytes_apply = 0;
-		stats->kernel[0] = 0;
-		stats->kernel_other[0] = 0;
-		stats->kernel_expand[0] = 0;
-		stats->ms_expand = stats->ms_pad = 0.0f;
-		stats->bytes_expand = stats->bytes_staged = 0;
-		stats->used_sparse_image = want_sp ? 1 : 0;
-		stats->sparse_image_built = built_sp ? 1 : 0;
-		stats->ms_sparse_build = stats->ms_sparse_apply = stats->ms_sparse_gather = 0.0f;
-		stats->sparse_image_nnz = stats->sparse_image_ops_build = stats->sparse_image_ops_apply = 0;
-		stats->sparse_image_levels = stats->sparse_image_launches = 0;
-		stats->bytes_sparse_build = stats->bytes_sparse_apply = stats->bytes_sparse_gather = 0;
-		if (want_sp) {
-			const SpImage &P = F->sp;
-			if (built_sp)
-				HIP_CHECK(hipEventElapsedTime(&stats->ms_sparse_build, P.ev0, P.ev1));
-			HIP_CHECK(hipEventElapsedTime(&stats->ms_sparse_apply, W->ev[5], W->ev[6]));
-			HIP_CHECK(hipEventElapsedTime(&stats->ms_sparse_gather, W->ev[6], W->ev[1]));
-			stats->sparse_image_nnz = P.nnz;
-			stats->sparse_image_ops_build = P.ops_build;
-			stats->sparse_image_ops_apply = (i64) ctr64[C64_STREAM];
-			stats->sparse_image_levels = P.nlevels;
-			stats->sparse_image_launches = P.launches;
-			// algorithmic bytes.  Build: every fragment entry read once per row that uses it and written
-			// once (4 B each), the fragment words (8 B per dependency and segment + 8 B per row and segment), the entries of U'.
-			// Rows of S: the fragment entries read (4 B), a fragment word per pivotal entry and segment, the entries in and the
-			// fragments of S out (4 B); gather: fragments in (4 B), pairs out (8 B), 8 B per (row, segment).
-			stats->bytes_sparse_build = 4 * (P.ops_build + P.nnz) + 8 * (P.ndeps + (i64) P.r) * P.nseg + 8 * F->nnz;
-			stats->bytes_sparse_apply = 4 * (i64) ctr64[C64_STREAM] + 8 * (i64) ctr64[C64_ELIM] * P.nseg + 8 * (i64) ctr64[C64_INPUT] + 4 * total +
-			                            8 * (i64) nrows * P.nseg;
-			stats->bytes_sparse_gather = 12 * total + 8 * (i64) nrows * P.nseg + 8 * (i64) nrows;
-			const bool build_dominates = stats->ms_sparse_build > stats->ms_sparse_apply;
-			snprintf(stats->kernel, sizeof(stats->kernel), "%s", build_dominates ? "sp_build_kernel" : "sp_apply_kernel");
-			snprintf(stats->kernel_other, sizeof(stats->kernel_other), "%s", build_dominates ? "sp_apply_kernel" : "sp_build_kernel");
-			snprintf(stats->kernel_expand, sizeof(stats->kernel_expand), "sp_gather_kernel");
-		} else if (used_bs) {
-			const BsImage &B = F->bs;
-			if (built_bs) {
-				HIP_CHECK(hipEventElapsedTime(&stats->ms_backsolve, B.ev0, B.ev1));
-				// every row of R written once and read once per dependency; the entries of U' read once
-				stats->bytes_backsolve = ((i64) B.r + B.ndeps) * (i64) B.Sm * B.elem_bytes + 8 * F->nnz;
-			}
-			HIP_CHECK(hipEventElapsedTime(&stats->ms_apply, W->ev[5], W->ev[1]));
-			// one row of R per pivotal entry of the reduced rows, the entries in and out, 20 B per row
-			stats->bytes_apply = (i64) ctr64[C64_ELIM] * (i64) B.Sm * B.elem_bytes + 8 * ((i64) ctr64[C64_INPUT] + total) + 20 * (i64) nrows;
-			if (bs_staged_slices > 0) {
-				// staged output: the entries of S leave through bs_expand_s16_kernel; with one slice the two kernels are timed apart
-				stats->bytes_apply -= 8 * total;
-				stats->bytes_expand = 8 * total;
-				stats->bytes_staged = (i64) nrows * B.ldR * B.elem_bytes;
-				snprintf(stats->kernel_expand, sizeof(stats->kernel_expand), "bs_expand_kernel<%d>", B.sgn ? 0 : B.elem_bytes == 2 ? 1 : 2);
-				if (bs_staged_slices == 1) {
-					HIP_CHECK(hipEventElapsedTime(&stats->ms_apply, W->ev[5], W->ev[6]));
-					HIP_CHECK(hipEventElapsedTime(&stats->ms_expand, W->ev[6], W->ev[1]));
-				}
-			}
-			char apply_name[32];
-			if (B.sgn && bs_csr_tiles == 0)          // (the CSR output's two-buffer kernel: wide rows, A/B runs)
-				snprintf(apply_name, sizeof(apply_name), "bs_apply_s16_kernel<lds2>");
-			else if (B.sgn)
-				snprintf(apply_name, sizeof(apply_name), "bs_apply_s16_kernel");
-			else
-				snprintf(apply_name, sizeof(apply_name), "bs_apply_kernel<%s,%s>", B.elem_bytes == 2 ? "true" : "false", B.plain ? "true" : "false");
-			const bool build_dominates = stats->ms_backsolve > stats->ms_apply;
-			snprintf(stats->kernel, sizeof(stats->kernel), "%s", build_dominates ? B.kernel_build : apply_name);
-			snprintf(stats->kernel_other, sizeof(stats->kernel_other), "%s", build_dominates ? apply_name : B.kernel_build);
-		} else if (group_mode && use_pull) {
-			snprintf(stats->kernel, sizeof(stats->kernel), "schur_pull_kernel");
-		} else if (group_mode && !stats->group_aborted) {
-			schur_group_variant_name(F->rpad, wide_dense, group_waves, stats->kernel, sizeof(stats->kernel));
-		} else {
-			snprintf(stats->kernel, sizeof(stats->kernel), "schur_wave_dense_kernel<%s>", wide_dense ? "true" : "false");
-		}
-		if (nrows > 0 && !used_bs && !want_sp) {
-			if (group_mode)
-				HIP_CHECK(hipEventElapsedTime(&stats->ms_group, W->ev[0], W->ev[5]));
-			HIP_CHECK(hipEventElapsedTime(&stats->ms_tier0, group_mode ? W->ev[5] : W->ev[0], W->ev[3]));
-			HIP_CHECK(hipEventElapsedTime(&stats->ms_tier1, W->ev[3], W->ev[4]));
-			HIP_CHECK(hipEventElapsedTime(&stats->ms_tier2, W->ev[4], W->ev[1]));
-		}
-		HIP_CHECK(hipEventElapsedTime(&stats->ms_finalize, W->ev[1], W->ev[2]));
-		HIP_CHECK(hipEventElapsedTime(&stats->ms_total, W->ev[0], W->ev[2]));
-		if (built_sp) {          // (the sparse image is built before the events of the call start: its time belongs to the call)
-			stats->ms_total += stats->ms_sparse_build;
-			stats->ms_eliminate += stats->ms_sparse_build;
-		}
-	}
-	return status;
+		Lout->used = (i64) rb.ctr64[C64_LPOOL];
+	if (stats != nullptr)
+		write_stats(stats, route, done, F, W, nrows, rb);
+	return rb.ctr[CTR_STATUS] & 3;      // bit 0: row pool exhausted, bit 1: L pool exhausted
 }
 }  // namespace
 
@@ -2299,7 +2376,7 @@ void spasm_hip_dschur_row_pointers(const spasm_hip_dwork *W, i64 *d_Sp, void *st
 void spasm_hip_dschur_fetch(const spasm_hip_dwork *W, i64 *d_Sp, int *d_Sj, spasm_ZZp *d_Sx, void *stream_)
 {
 	hipStream_t stream = (hipStream_t) stream_;
-	HIP_CHECK(hipMemcpyAsync(d_Sp, W->d_Sp, ((size_t) W->last_rows + 1) * sizeof(i64), hipMemcpyDefault, stream));
+	spasm_hip_dschur_row_pointers(W, d_Sp, stream_);
 	if (W->last_nnz > 0) {
 		HIP_CHECK(hipMemcpyAsync(d_Sj, W->d_Sj, (size_t) W->last_nnz * sizeof(int), hipMemcpyDefault, stream));
 		HIP_CHECK(hipMemcpyAsync(d_Sx, W->d_Sx, (size_t) W->last_nnz * sizeof(int), hipMemcpyDefault, stream));
@@ -2313,9 +2390,15 @@ void spasm_hip_dschur_fetch(const spasm_hip_dwork *W, i64 *d_Sp, int *d_Sj, spas
 // Every rank: its slab problem (host: spasm_hip_column_slab -- A and U with the other ranks' non-pivotal columns deleted),
 // its image, ALL n rows reduced on it (the ordinary one-GPU call below, communicator set aside), columns mapped back,
 // all-gatherv of the slabs, stitched into whole rows on every device, then downloaded / kept resident like any result.
-extern "C" {
 static struct spasm_csr *schur_entry(const struct spasm_csr *A, const int *p, int n, const struct spasm_lu *fact, double est_density, struct spasm_triplet *L,
                                      const int *p_in, int *p_out, spasm_hip_dwork **keep_on_device);
+
+// p_out[k] = the row of the caller's matrix that row k of S comes from
+static void rows_of_origin(int *p_out, const int *p_in, const int *p, int n)
+{
+	if (p_out != nullptr)
+		for (int k = 0; k < n; k++)
+			p_out[k] = (p_in != nullptr) ? p_in[p[k]] : p[k];
 }
 
 static struct spasm_csr *schur_by_column_slabs(const struct spasm_csr *A, const int *p, int n, const struct spasm_lu *fact, double est_density,
@@ -2367,9 +2450,7 @@ static struct spasm_csr *schur_by_column_slabs(const struct spasm_csr *A, const 
 		W->d_Sx = nullptr;
 		sh::big_free(d_cols);
 		spasm_hip_dwork_destroy(W);
-		if (p_out != nullptr)
-			for (int k = 0; k < n; k++)
-				p_out[k] = (p_in != nullptr) ? p_in[p[k]] : p[k];
+		rows_of_origin(p_out, p_in, p, n);
 		const double density = (n > 0 && m > 0) ? (double) total / ((double) m * n) : 0.0;
 		logmsg("Schur complement: %d * %d [%" PRId64 " nz / density= %.3f], %.1fs (split by columns: rank %d of %d holds its slab of %d of the %d non-pivotal columns, "
 		       "%" PRId64 " entries, on the device; slab problem %.2fs)\n", n, m, total, density, wtime() - t0, rank, world, mm - fact->U->n, m - fact->U->n, snz, t_slab);
@@ -2389,10 +2470,8 @@ static struct spasm_csr *schur_by_column_slabs(const struct spasm_csr *A, const 
 	i64 *dSp = dalloc<i64>((i64) n + 1);
 	int *dSj = static_cast<int *>(big_alloc((size_t) std::max<i64>(total, 1) * sizeof(int)));
 	int *dSx = static_cast<int *>(big_alloc((size_t) std::max<i64>(total, 1) * sizeof(int)));
-	if (W->d_lb_status == nullptr)
-		W->d_lb_status = dalloc<unsigned long long>((i64) W->max_rows + 16 + 16 * 16);
 	HIP_CHECK(hipMemsetAsync(W->d_ctr, 0, CTR_COUNT * sizeof(int), stream));
-	launch_stitch_slabs(gSp, gSj, gSx, n, world, dSp, dSj, dSx, total, W->d_row_len, W->d_lb_status, W->d_ctr, stream);
+	launch_stitch_slabs(gSp, gSj, gSx, n, world, dSp, dSj, dSx, total, W->d_row_len, lookback_buffer(W), W->d_ctr, stream);
 	struct spasm_csr *S = spasm_hip_csr_alloc(n, m, total, prime, true);
 	HIP_CHECK(hipMemcpyAsync(S->p, dSp, ((size_t) n + 1) * sizeof(i64), hipMemcpyDeviceToHost, stream));
 	HIP_CHECK(hipStreamSynchronize(stream));
@@ -2416,9 +2495,7 @@ static struct spasm_csr *schur_by_column_slabs(const struct spasm_csr *A, const 
 	sh::big_free(gSx);
 	sh::big_free(d_cols);
 	spasm_hip_dwork_destroy(W);
-	if (p_out != nullptr)
-		for (int k = 0; k < n; k++)
-			p_out[k] = (p_in != nullptr) ? p_in[p[k]] : p[k];
+	rows_of_origin(p_out, p_in, p, n);
 	const double density = (n > 0 && m > 0) ? (double) total / ((double) m * n) : 0.0;
 	logmsg("Schur complement: %d * %d [%" PRId64 " nz / density= %.3f], %.1fs (split by columns: rank %d of %d reduced every row on %d of the %d "
 	       "non-pivotal columns; slab problem %.2fs)\n", n, m, total, density, wtime() - t0, rank, world, mm - fact->U->n, m - fact->U->n, t_slab);
@@ -2428,13 +2505,229 @@ static struct spasm_csr *schur_by_column_slabs(const struct spasm_csr *A, const 
 // --------------------------------------------------------------------------
 // host-pointer drop-in for spasm_schur
 // --------------------------------------------------------------------------
-static struct spasm_csr *schur_entry(const struct spasm_csr *A, const int *p, int n, const struct spasm_lu *fact, double est_density, struct spasm_triplet *L,
-                                     const int *p_in, int *p_out, spasm_hip_dwork **keep_on_device);
-
-struct spasm_csr *spasm_hip_schur(const struct spasm_csr *A, const int *p, int n, const struct spasm_lu *fact,
-                                  double est_density, struct spasm_triplet *L, const int *p_in, int *p_out)
+// Two ways to share a batch between ranks.  By COLUMNS when the factor takes an image path -- the sparse
+// image or the dense one: the columns of R and of S never meet, so rank k builds only ITS slab of R and reduces all rows on it;
+// nothing is replicated --, by ROWS otherwise (the row-by-row kernels: rows never meet; with an image every rank would
+// rebuild all of R).  SPASM_HIP_SHARD=rows|columns forces one.  The choice is made BEFORE the image of the whole factor is
+// planned -- it hangs on the sizes alone (r, Sm, nnz(U), p), through the rules spasm_hip_dfact_create plans by
+// (sh::sparse_image_plan_rule, sh::dense_image_plan_rule) --, so that a rank of a column split never plans, hashes or uploads
+// more than its own slab (round 4 planned the full image on every rank first).
+static bool shard_by_columns(const struct spasm_lu *fact, int m, i64 prime, spasm_hip_comm *comm)
 {
-	return schur_entry(A, p, n, fact, est_density, L, p_in, p_out, nullptr);
+	const int r_all = fact->U->n, Sm_all = m - fact->U->n;
+	bool shard_cols = false;
+	const char *how = sh::env_get("SPASM_HIP_SHARD");
+	if (how != nullptr && std::strcmp(how, "columns") == 0) {
+		shard_cols = true;
+	} else if (how == nullptr || std::strcmp(how, "rows") != 0) {
+		int64_t bs_bytes = 0;
+		const bool has_sparse_plan = sparse_image_plan_rule(prime, r_all, Sm_all);
+		const bool has_dense_plan = dense_image_plan_rule(prime, r_all, Sm_all, fact->U->p[r_all] - r_all, &bs_bytes);
+		shard_cols = has_sparse_plan || has_dense_plan;
+	}
+	return shard_cols && Sm_all >= comm_world(comm);
+}
+
+// A full batch through the sparse image: the pool of S is sized from the image itself.  The driver's estimate comes from
+// 100 rows (spasm_schur_estimate_density) and the rows of these Schur complements differ by orders of magnitude: mk15.b4
+// was given 2.54e9 entries for 1.86e9 in one call and too few in another -- and a pool that is too small means the whole
+// call again on a fresh block of twice the size (tens of GB that the device has to map: the 2.2 s sparse round in one
+// call of five of round 4's bench, where the others took 0.07).  Here R is built first and 16,384 rows spread over the
+// batch go through it (under a millisecond): their entries, scaled, + 15 % + what the waves strand in their arenas
+// (8,192 rows + 12 % still fell short once in fifteen mk14.b4 calls).
+// Returns the pool to take (`pool` itself when the batch does not go that way) and the device time of the sample.
+static i64 pool_from_sparse_sample(const spasm_hip_dcsr &dA, const int *p, int n, spasm_hip_dfact *F, double est_density, i64 pool, i64 pool_max,
+                                   double *ms_sample, hipStream_t stream)
+{
+	if (n < 65536 || !sparse_image_wanted(F, row_path_forced(), n) || !(F->sp.valid || sparse_image_build(F, stream)))
+		return pool;
+	const int ns = 16384, m = dA.m;
+	std::vector<int> sample((size_t) ns);
+	for (int k = 0; k < ns; k++)
+		sample[(size_t) k] = p[(i64) k * n / ns];
+	int *d_sample = dalloc<int>(ns);
+	upload(d_sample, sample.data(), ns, stream);
+	const i64 spool_max = (i64) ns * (i64) (m - F->r) + (i64) 4096 * 4096;
+	i64 spool = std::min(spool_max, std::max<i64>((i64) (4.0 * est_density * ns * (double) (m - F->r)), (i64) 1 << 24) + (i64) 4096 * 4096);
+	for (;;) {
+		spasm_hip_dwork *Ws = spasm_hip_dwork_create(ns, m, spool);
+		spasm_hip_schur_stats sts{};
+		const int rc = dschur_impl(&dA, d_sample, ns, F, Ws, stream, &sts, nullptr);
+		spasm_hip_dwork_destroy(Ws);
+		if (rc == 0) {
+			*ms_sample = sts.ms_total;
+			if (sts.used_sparse_image && sts.nnz > 0) {
+				const i64 sized = (i64) (1.15 * (double) sts.nnz / (double) ns * (double) n) + (i64) 48 * 1024 * 1024;
+				if (verbose() >= 2)
+					logmsg("[schur/hip] pool of S: %" PRId64 " entries from %d sampled rows through the sparse image (%.1f per row), %" PRId64 " from the driver's estimate\n",
+					       sized, ns, (double) sts.nnz / ns, pool);
+				pool = std::min(pool_max, sized);
+				counters()[CNT_POOL_RESIZED] += 1;
+			}
+			break;
+		}
+		if (spool >= spool_max)
+			break;
+		spool = std::min(spool_max, 2 * spool);
+	}
+	sh::big_free(d_sample);
+	return pool;
+}
+
+// L requested: device pools for the elimination coefficients, grown on demand by the retry loop of the call
+struct LPools {
+	LOut out;
+	int *d_row_orig = nullptr;
+
+	LPools(const int *p_in, const int *p, int n, i64 in_nnz, hipStream_t stream)
+	{
+		out.cap = std::max<i64>(16 * in_nnz, (i64) 1 << 24);
+		std::vector<int> ro((size_t) (n > 0 ? n : 1));
+		rows_of_origin(ro.data(), p_in, p, n);
+		d_row_orig = dalloc<int>(n);
+		upload(d_row_orig, ro.data(), n, stream);
+		HIP_CHECK(hipStreamSynchronize(stream));
+		out.row_orig = d_row_orig;
+	}
+	~LPools()
+	{
+		free();
+		sh::big_free(d_row_orig);
+	}
+	void alloc(hipStream_t stream)
+	{
+		for (int **pool : {&out.Li, &out.Lj, &out.Lx})
+			*pool = dalloc<int>(out.cap);
+		HIP_CHECK(hipMemsetAsync(out.Li, 0xFF, (size_t) out.cap * sizeof(int), stream));
+	}
+	void free()
+	{
+		for (int **pool : {&out.Li, &out.Lj, &out.Lx}) {
+			sh::big_free(*pool);
+			*pool = nullptr;
+		}
+	}
+	// the coefficient triplets to the host, appended to L; slots never written still hold -1
+	void append_to(struct spasm_triplet *L) const
+	{
+		const i64 used = std::min(out.used, out.cap);
+		std::vector<int> hi((size_t) (used > 0 ? used : 1)), hj((size_t) (used > 0 ? used : 1)), hx((size_t) (used > 0 ? used : 1));
+		if (used > 0) {
+			HIP_CHECK(hipMemcpy(hi.data(), out.Li, (size_t) used * sizeof(int), hipMemcpyDeviceToHost));
+			HIP_CHECK(hipMemcpy(hj.data(), out.Lj, (size_t) used * sizeof(int), hipMemcpyDeviceToHost));
+			HIP_CHECK(hipMemcpy(hx.data(), out.Lx, (size_t) used * sizeof(int), hipMemcpyDeviceToHost));
+		}
+		i64 extra = 0;
+		for (i64 t = 0; t < used; t++)
+			extra += hi[t] >= 0;
+		if (L->nz + extra > L->nzmax)
+			spasm_hip_triplet_realloc(L, 2 * L->nzmax + extra);
+		for (i64 t = 0; t < used; t++) {
+			if (hi[t] < 0)
+				continue;
+			L->i[L->nz] = hi[t];
+			L->j[L->nz] = hj[t];
+			L->x[L->nz] = hx[t];
+			L->nz += 1;
+		}
+	}
+};
+
+// The call on a fresh workspace, again with larger pools while one of them is too small (the row pool of S: *pool, doubled up
+// to pool_max; the pools of L: four times the size).  Returns the workspace that holds the result.
+static spasm_hip_dwork *call_with_growing_pools(const spasm_hip_dcsr &dA, const int *drows, int n, spasm_hip_dfact *F, i64 *pool_io, i64 pool_max, LPools *lpools,
+                                                spasm_hip_schur_stats *st, double *t_wcreate, hipStream_t stream)
+{
+	i64 pool = *pool_io;
+	for (;;) {
+		if (lpools != nullptr)
+			lpools->alloc(stream);
+		const double tw0 = wtime();
+		spasm_hip_dwork *W = spasm_hip_dwork_create(n, dA.m, pool);
+		*t_wcreate += wtime() - tw0;
+		// one-shot call: allocating tens of GB costs more than the kernel gains from having every
+		// row group resident at once (hipMalloc is ~30 ms per GB); the device-level API keeps its
+		// workspace and takes the large budget
+		W->scratch_budget = (i64) 24 << 30;
+		scratch_adopt(W);
+		const int rc = dschur_impl(&dA, drows, n, F, W, stream, st, lpools != nullptr ? &lpools->out : nullptr);
+		if (rc == 0) {
+			// what the row-by-row kernels measured feeds the path choice of the next, larger batch on the same factor
+			if (!st->used_backsolve && !st->used_sparse_image && n >= 64 && st->eliminations > 0)
+				F->bs.elim_hint = (double) st->eliminations / (double) n;
+			*pool_io = pool;
+			return W;
+		}
+		scratch_park(W);
+		spasm_hip_dwork_destroy(W);
+		if (lpools != nullptr)
+			lpools->free();
+		if (rc & 1) {
+			if (pool >= pool_max)
+				die("spasm_hip_schur: pool of %" PRId64 " entries still too small", pool);
+			pool = std::min(pool_max, 2 * pool + dA.m);
+			counters()[CNT_POOL_RETRIES] += 1;
+			logmsg("[schur/hip] pool too small, retrying with %" PRId64 " entries\n", pool);
+		}
+		if ((rc & 2) && lpools != nullptr) {
+			lpools->out.cap *= 4;
+			logmsg("[schur/hip] L pool too small, retrying with %" PRId64 " entries\n", lpools->out.cap);
+		}
+	}
+}
+
+// ---- delivery of the result of a call: kept on the device, gathered over the ranks, or downloaded and / or adopted as resident ----
+
+// all-gatherv of the ranks' slices (sizes first, then exact-count broadcasts), then one download of the whole
+static struct spasm_csr *deliver_gathered(spasm_hip_comm *comm, spasm_hip_dwork *W, int n_all, int m, i64 prime, hipStream_t stream)
+{
+	i64 total = 0;
+	int rows_all = 0;
+	(void) spasm_hip_dschur_allgatherv(comm, W, nullptr, nullptr, nullptr, -1, &rows_all, &total, stream);
+	if (rows_all != n_all)
+		die("spasm_hip_schur: the ranks reduced %d rows in all, %d expected", rows_all, n_all);
+	i64 *gSp = dalloc<i64>((i64) n_all + 1);
+	int *gSj = dalloc<int>(total);
+	int *gSx = dalloc<int>(total);
+	if (spasm_hip_dschur_allgatherv(comm, W, gSp, gSj, gSx, total, nullptr, nullptr, stream) != 0)
+		die("spasm_hip_schur: all-gatherv of the slices failed");
+	struct spasm_csr *S = spasm_hip_csr_alloc(n_all, m, total, prime, true);
+	HIP_CHECK(hipMemcpy(S->p, gSp, ((size_t) n_all + 1) * sizeof(i64), hipMemcpyDeviceToHost));
+	if (total > 0) {
+		HIP_CHECK(hipMemcpy(S->j, gSj, (size_t) total * sizeof(int), hipMemcpyDeviceToHost));
+		HIP_CHECK(hipMemcpy(S->x, gSx, (size_t) total * sizeof(int), hipMemcpyDeviceToHost));
+	}
+	if (resident_enabled() && n_all >= 1024) {
+		resident_adopt(S, gSp, gSj, gSx, false);          // the next round's A is already on every device
+	} else {
+		sh::big_free(gSp);
+		sh::big_free(gSj);
+		sh::big_free(gSx);
+	}
+	return S;
+}
+
+// one device: the row pointers come to the host, the entries too unless they stay behind as the resident A of the next round
+// (*lazy: row pointers only)
+static struct spasm_csr *deliver_downloaded(spasm_hip_dwork *W, int n, int m, i64 nnz, i64 prime, bool may_be_lazy, bool *lazy, hipStream_t stream)
+{
+	struct spasm_csr *S = spasm_hip_csr_alloc(n, m, nnz, prime, true);
+	sh::d2h(S->p, W->d_Sp, ((size_t) n + 1) * sizeof(i64), stream);
+	const bool keep = resident_enabled() && n >= 1024;
+	*lazy = keep && g_lazy_download && may_be_lazy;
+	if (nnz > 0 && !*lazy) {
+		HIP_CHECK(hipMemcpy(S->j, W->d_Sj, (size_t) nnz * sizeof(int), hipMemcpyDeviceToHost));
+		HIP_CHECK(hipMemcpy(S->x, W->d_Sx, (size_t) nnz * sizeof(int), hipMemcpyDeviceToHost));
+	}
+	if (keep) {
+		// keep the result where it was computed -- it is the A of the next round: the table takes the workspace's arrays
+		// over (no copy; they are sized for the estimate, a little more than the result)
+		resident_adopt(S, W->d_Sp, W->d_Sj, W->d_Sx, *lazy);
+		W->d_Sp = nullptr;
+		W->d_Sj = nullptr;
+		W->d_Sx = nullptr;
+	}
+	return S;
 }
 
 // keep_on_device != NULL: one device, no communicator, no download -- the workspace that holds the result (W->d_Sp / d_Sj / d_Sx,
@@ -2455,38 +2748,18 @@ static struct spasm_csr *schur_entry(const struct spasm_csr *A, const int *p, in
 	// slices are reassembled on the devices.  Small batches (density samples) and calls that record L are not sharded:
 	// every rank computes them whole, which keeps the ranks in step without a collective.
 	spasm_hip_comm *comm = (keep_on_device != nullptr) ? nullptr : current_comm();
-	int lo = 0, hi = n;
 	const bool shard = comm != nullptr && L == nullptr && (comm_world(comm) > 1 || env_int("SPASM_HIP_SHARD_FORCE", 0) != 0) &&
 	                   n >= env_int("SPASM_HIP_SHARD_MIN_ROWS", 2048) * comm_world(comm);
-	// Two ways to share a batch.  By COLUMNS when the factor takes an image path -- the sparse image or
-	// the dense one: the columns of R and of S never meet, so rank k builds only ITS slab of R and reduces all rows on it;
-	// nothing is replicated --, by ROWS otherwise (the row-by-row kernels: rows never meet; with an image every rank would
-	// rebuild all of R).  SPASM_HIP_SHARD=rows|columns forces one.  The choice is made BEFORE the image of the whole factor is
-	// planned -- it hangs on the sizes alone (r, Sm, nnz(U), p: the rules of spasm_hip_dfact_create) --, so that a rank of a
-	// column split never plans, hashes or uploads more than its own slab (round 4 planned the full image on every rank first).
-	if (shard) {
-		const int r_all = fact->U->n, Sm_all = m - fact->U->n;
-		bool shard_cols = false;
-		const char *how = sh::env_get("SPASM_HIP_SHARD");
-		if (how != nullptr && std::strcmp(how, "columns") == 0) {
-			shard_cols = true;
-		} else if (how == nullptr || std::strcmp(how, "rows") != 0) {
-			int64_t bs_bytes = 0;
-			const bool has_sparse_plan = sparse_image_possible(prime) && r_all > 0 && Sm_all > 0 &&
-			                             (env_int("SPASM_HIP_SPARSE_IMAGE", -1) == 1 || (Sm_all >= 8192 && (double) r_all * (double) Sm_all >= 5e8));
-			const bool has_dense_plan = env_int("SPASM_HIP_BACKSOLVE", -1) != 0 && backsolve_eligible(r_all, Sm_all, fact->U->p[r_all] - r_all, &bs_bytes, prime);
-			shard_cols = has_sparse_plan || has_dense_plan;
-		}
-		if (shard_cols && Sm_all >= comm_world(comm))
-			return schur_by_column_slabs(A, p, n, fact, est_density, p_in, p_out, comm);
-	}
+	if (shard && shard_by_columns(fact, m, prime, comm))
+		return schur_by_column_slabs(A, p, n, fact, est_density, p_in, p_out, comm);
+	// factor image
 	spasm_hip_dfact *F = cached_dfact(fact->U, fact->qinv, stream);
 	if (est_density >= 0)
 		F->bs.density_hint = est_density;      // (a dense result is cheaper through the back-substituted image)
 	const double t_fact = wtime() - t0;
-	// device image of A and of the row list
-	const i64 annz = A->p[A->n];
+	// device image of A and of the row list (this rank's share of it)
 	DeviceMatrix devA(A, stream);
+	int lo = 0, hi = n;
 	if (shard)
 		spasm_hip_shard(n, comm_rank(comm), comm_world(comm), &lo, &hi);
 	const int n_all = n;
@@ -2495,205 +2768,44 @@ static struct spasm_csr *schur_entry(const struct spasm_csr *A, const int *p, in
 	n = hi - lo;
 	int *drows = dalloc<int>(n);
 	upload(drows, p, n, stream);
-	spasm_hip_dcsr dA{A->n, m, annz, devA.p, devA.j, devA.x};
-
+	spasm_hip_dcsr dA{A->n, m, A->p[A->n], devA.p, devA.j, devA.x};
+	// pool of S
 	if (est_density < 0)
 		est_density = 0.0;     // the pool below is grown on demand instead of being estimated
 	i64 in_nnz = 0;
 	for (int k = 0; k < n; k++)
 		in_nnz += A->p[p[k] + 1] - A->p[p[k]];
 	// est_density is relative to the non-pivotal columns (spasm_schur_estimate_density divides by m - r)
-	i64 pool = std::max<i64>((i64) (est_density * n * (double) (m - F->r) * 1.3), 4 * in_nnz) + (i64) 4096 * 4096;
 	const i64 pool_max = (i64) n * (i64) (m - F->r) + (i64) 4096 * 4096;
-	pool = std::min(pool, pool_max);
-	spasm_hip_schur_stats st{};
-	spasm_hip_dwork *W = nullptr;
+	i64 pool = std::min(pool_max, std::max<i64>((i64) (est_density * n * (double) (m - F->r) * 1.3), 4 * in_nnz) + (i64) 4096 * 4096);
 	const double t1 = wtime();
-	double t_wcreate = 0.0;
-	// A full batch through the sparse image: the pool of S is sized from the image itself.  The driver's estimate comes from
-	// 100 rows (spasm_schur_estimate_density) and the rows of these Schur complements differ by orders of magnitude: mk15.b4
-	// was given 2.54e9 entries for 1.86e9 in one call and too few in another -- and a pool that is too small means the whole
-	// call again on a fresh block of twice the size (tens of GB that the device has to map: the 2.2 s sparse round in one
-	// call of five of round 4's bench, where the others took 0.07).  Here R is built first and 16,384 rows spread over the
-	// batch go through it (under a millisecond): their entries, scaled, + 15 % + what the waves strand in their arenas
-	// (8,192 rows + 12 % still fell short once in fifteen mk14.b4 calls).
-	double ms_sample = 0.0;
-	if (L == nullptr && !shard && n >= 65536 &&
-	    sparse_image_wanted(F, env_int("SPASM_HIP_FORCE_TIER", 0) != 0 || env_int("SPASM_HIP_GROUP", -1) >= 0, n) &&
-	    (F->sp.valid || sparse_image_build(F, stream))) {
-		const int ns = 16384;
-		std::vector<int> sample((size_t) ns);
-		for (int k = 0; k < ns; k++)
-			sample[(size_t) k] = p[(i64) k * n / ns];
-		int *d_sample = dalloc<int>(ns);
-		upload(d_sample, sample.data(), ns, stream);
-		const i64 spool_max = (i64) ns * (i64) (m - F->r) + (i64) 4096 * 4096;
-		i64 spool = std::min(spool_max, std::max<i64>((i64) (4.0 * est_density * ns * (double) (m - F->r)), (i64) 1 << 24) + (i64) 4096 * 4096);
-		for (;;) {
-			spasm_hip_dwork *Ws = spasm_hip_dwork_create(ns, m, spool);
-			spasm_hip_schur_stats sts{};
-			const int rc = dschur_impl(&dA, d_sample, ns, F, Ws, stream, &sts, nullptr);
-			spasm_hip_dwork_destroy(Ws);
-			if (rc == 0) {
-				ms_sample = sts.ms_total;
-				if (sts.used_sparse_image && sts.nnz > 0) {
-					const i64 sized = (i64) (1.15 * (double) sts.nnz / (double) ns * (double) n) + (i64) 48 * 1024 * 1024;
-					if (verbose() >= 2)
-						logmsg("[schur/hip] pool of S: %" PRId64 " entries from %d sampled rows through the sparse image (%.1f per row), %" PRId64 " from the driver's estimate\n",
-						       sized, ns, (double) sts.nnz / ns, pool);
-					pool = std::min(pool_max, sized);
-					counters()[CNT_POOL_RESIZED] += 1;
-				}
-				break;
-			}
-			if (spool >= spool_max)
-				break;
-			spool = std::min(spool_max, 2 * spool);
-		}
-		sh::big_free(d_sample);
-	}
-	// L requested: pools for the elimination coefficients, grown on demand
-	LOut lout;
-	i64 lcap = (L != nullptr) ? std::max<i64>(16 * in_nnz, (i64) 1 << 24) : 0;
-	int *d_row_orig = nullptr;
-	if (L != nullptr) {
-		std::vector<int> ro((size_t) (n > 0 ? n : 1));
-		for (int k = 0; k < n; k++)
-			ro[k] = (p_in != nullptr) ? p_in[p[k]] : p[k];
-		d_row_orig = dalloc<int>(n);
-		upload(d_row_orig, ro.data(), n, stream);
-		HIP_CHECK(hipStreamSynchronize(stream));
-	}
-	for (;;) {
-		if (L != nullptr) {
-			lout.row_orig = d_row_orig;
-			lout.cap = lcap;
-			lout.Li = dalloc<int>(lcap);
-			lout.Lj = dalloc<int>(lcap);
-			lout.Lx = dalloc<int>(lcap);
-			HIP_CHECK(hipMemsetAsync(lout.Li, 0xFF, (size_t) lcap * sizeof(int), stream));
-		}
-		const double tw0 = wtime();
-		W = spasm_hip_dwork_create(n, m, pool);
-		t_wcreate += wtime() - tw0;
-		// one-shot call: allocating tens of GB costs more than the kernel gains from having every
-		// row group resident at once (hipMalloc is ~30 ms per GB); the device-level API keeps its
-		// workspace and takes the large budget
-		W->scratch_budget = (i64) 24 << 30;
-		scratch_adopt(W);
-		const int rc = dschur_impl(&dA, drows, n, F, W, stream, &st, (L != nullptr) ? &lout : nullptr);
-		if (rc == 0) {
-			// what the row-by-row kernels measured feeds the path choice of the next, larger batch on the same factor
-			if (!st.used_backsolve && !st.used_sparse_image && n >= 64 && st.eliminations > 0)
-				F->bs.elim_hint = (double) st.eliminations / (double) n;
-			break;
-		}
-		scratch_park(W);
-		spasm_hip_dwork_destroy(W);
-		if (L != nullptr) {
-			sh::big_free(lout.Li);
-			sh::big_free(lout.Lj);
-			sh::big_free(lout.Lx);
-		}
-		if (rc & 1) {
-			if (pool >= pool_max)
-				die("spasm_hip_schur: pool of %" PRId64 " entries still too small", pool);
-			pool = std::min(pool_max, 2 * pool + m);
-			counters()[CNT_POOL_RETRIES] += 1;
-			logmsg("[schur/hip] pool too small, retrying with %" PRId64 " entries\n", pool);
-		}
-		if (rc & 2) {
-			lcap *= 4;
-			logmsg("[schur/hip] L pool too small, retrying with %" PRId64 " entries\n", lcap);
-		}
-	}
-	if (L != nullptr) {
-		// bring the coefficient triplets back; slots never written still hold -1
-		const i64 used = std::min(lout.used, lcap);
-		std::vector<int> hi((size_t) (used > 0 ? used : 1)), hj((size_t) (used > 0 ? used : 1)), hx((size_t) (used > 0 ? used : 1));
-		if (used > 0) {
-			HIP_CHECK(hipMemcpy(hi.data(), lout.Li, (size_t) used * sizeof(int), hipMemcpyDeviceToHost));
-			HIP_CHECK(hipMemcpy(hj.data(), lout.Lj, (size_t) used * sizeof(int), hipMemcpyDeviceToHost));
-			HIP_CHECK(hipMemcpy(hx.data(), lout.Lx, (size_t) used * sizeof(int), hipMemcpyDeviceToHost));
-		}
-		i64 extra = 0;
-		for (i64 t = 0; t < used; t++)
-			extra += hi[t] >= 0;
-		if (L->nz + extra > L->nzmax)
-			spasm_hip_triplet_realloc(L, 2 * L->nzmax + extra);
-		for (i64 t = 0; t < used; t++) {
-			if (hi[t] < 0)
-				continue;
-			L->i[L->nz] = hi[t];
-			L->j[L->nz] = hj[t];
-			L->x[L->nz] = hx[t];
-			L->nz += 1;
-		}
-		sh::big_free(lout.Li);
-		sh::big_free(lout.Lj);
-		sh::big_free(lout.Lx);
-		sh::big_free(d_row_orig);
+	double t_wcreate = 0.0, ms_sample = 0.0;
+	if (L == nullptr && !shard)
+		pool = pool_from_sparse_sample(dA, p, n, F, est_density, pool, pool_max, &ms_sample, stream);
+	// the call, again with larger pools while one of them is too small
+	std::unique_ptr<LPools> lpools;
+	if (L != nullptr)
+		lpools = std::make_unique<LPools>(p_in, p, n, in_nnz, stream);
+	spasm_hip_schur_stats st{};
+	spasm_hip_dwork *W = call_with_growing_pools(dA, drows, n, F, &pool, pool_max, lpools.get(), &st, &t_wcreate, stream);
+	if (lpools) {
+		lpools->append_to(L);
+		lpools.reset();
 	}
 	const double t_run = wtime() - t1;
+	// deliver
 	const double t2 = wtime();
-	struct spasm_csr *S = nullptr;
-	bool lazy = false;
 	if (keep_on_device != nullptr) {
-		scratch_park(W);
+		scratch_park(W);          // (kept on the device: the workspace that holds the result goes to the caller)
 		sh::big_free(drows);
-		W->last_rows = n;
-		W->last_nnz = st.nnz;
 		*keep_on_device = W;
 		logmsg("Schur complement (kept on the device): %d * %d [%" PRId64 " nz], %.1fs (GPU kernels %.1f ms, %s; factor image %.2fs, alloc+run %.2fs)\n", n, m, (i64) st.nnz,
 		       wtime() - t0, st.ms_total + ms_sample, st.kernel, t_fact, t_run);
 		return nullptr;
 	}
-	if (shard) {
-		// all-gatherv of the slices (sizes first, then exact-count broadcasts), then one download of the whole
-		i64 total = 0;
-		int rows_all = 0;
-		(void) spasm_hip_dschur_allgatherv(comm, W, nullptr, nullptr, nullptr, -1, &rows_all, &total, stream);
-		if (rows_all != n_all)
-			die("spasm_hip_schur: the ranks reduced %d rows in all, %d expected", rows_all, n_all);
-		i64 *gSp = dalloc<i64>((i64) n_all + 1);
-		int *gSj = dalloc<int>(total);
-		int *gSx = dalloc<int>(total);
-		if (spasm_hip_dschur_allgatherv(comm, W, gSp, gSj, gSx, total, nullptr, nullptr, stream) != 0)
-			die("spasm_hip_schur: all-gatherv of the slices failed");
-		S = spasm_hip_csr_alloc(n_all, m, total, prime, true);
-		HIP_CHECK(hipMemcpy(S->p, gSp, ((size_t) n_all + 1) * sizeof(i64), hipMemcpyDeviceToHost));
-		if (total > 0) {
-			HIP_CHECK(hipMemcpy(S->j, gSj, (size_t) total * sizeof(int), hipMemcpyDeviceToHost));
-			HIP_CHECK(hipMemcpy(S->x, gSx, (size_t) total * sizeof(int), hipMemcpyDeviceToHost));
-		}
-		if (resident_enabled() && n_all >= 1024) {
-			resident_adopt(S, gSp, gSj, gSx, false);          // the next round's A is already on every device
-		} else {
-			sh::big_free(gSp);
-			sh::big_free(gSj);
-			sh::big_free(gSx);
-		}
-	} else {
-		S = spasm_hip_csr_alloc(n, m, st.nnz, prime, true);
-		sh::d2h(S->p, W->d_Sp, ((size_t) n + 1) * sizeof(i64), stream);
-		const bool keep = resident_enabled() && n >= 1024;
-		lazy = keep && g_lazy_download && L == nullptr;
-		if (st.nnz > 0 && !lazy) {
-			HIP_CHECK(hipMemcpy(S->j, W->d_Sj, (size_t) st.nnz * sizeof(int), hipMemcpyDeviceToHost));
-			HIP_CHECK(hipMemcpy(S->x, W->d_Sx, (size_t) st.nnz * sizeof(int), hipMemcpyDeviceToHost));
-		}
-		if (keep) {
-			// keep the result where it was computed -- it is the A of the next round: the table takes the workspace's arrays
-			// over (no copy; they are sized for the estimate, a little more than the result)
-			resident_adopt(S, W->d_Sp, W->d_Sj, W->d_Sx, lazy);
-			W->d_Sp = nullptr;
-			W->d_Sj = nullptr;
-			W->d_Sx = nullptr;
-		}
-	}
-	if (p_out != nullptr)
-		for (int k = 0; k < n_all; k++)
-			p_out[k] = (p_in != nullptr) ? p_in[p_all[k]] : p_all[k];
+	bool lazy = false;
+	struct spasm_csr *S = shard ? deliver_gathered(comm, W, n_all, m, prime, stream) : deliver_downloaded(W, n, m, st.nnz, prime, L == nullptr, &lazy, stream);
+	rows_of_origin(p_out, p_in, p_all, n_all);
 	const double t_down = wtime() - t2;
 	const double t3 = wtime();
 	scratch_park(W);
@@ -2708,6 +2820,12 @@ static struct spasm_csr *schur_entry(const struct spasm_csr *A, const int *p, in
 		logmsg("[schur/hip] of alloc+run: %.2fs allocating the workspace (%" PRId64 " pool entries), scratch %.1f GB\n", t_wcreate, pool,
 		       (double) g_scratch_cache.bytes / 1073741824.0);
 	return S;
+}
+
+struct spasm_csr *spasm_hip_schur(const struct spasm_csr *A, const int *p, int n, const struct spasm_lu *fact,
+                                  double est_density, struct spasm_triplet *L, const int *p_in, int *p_out)
+{
+	return schur_entry(A, p, n, fact, est_density, L, p_in, p_out, nullptr);
 }
 
 // ... and spasm_hip_schur the way the driver calls it between two rounds (host_echelonize.cpp): residency on, the entries of S left on

@@ -61,7 +61,7 @@ REGIMES = [
     ("row-panel extend: Barrett quotient through __umul24", "dense_kernels.hip",
      "const bool q24 = F.p >= 256;", lambda p: p < 256, (251, 257)),
     ("row-by-row Schur: narrow LDS tables", "schur_api.hip",
-     "const bool wide_lds = ((double) F->prime * 6146.0 >= 4294967296.0);", lambda p: p * 6146 < TWO32, (698821, 698827)),
+     "wide_lds = ((double) F->prime * 6146.0 >= 4294967296.0);", lambda p: p * 6146 < TWO32, (698821, 698827)),
     ("row-by-row Schur: 6,144 + 1 terms per LDS slot", "schur_kernels.hip",
      "constexpr int CAPK = (H * 3) / 4 - 64;", lambda p: p * 6146 < TWO32, (698821, 698827)),
     ("x.A, solve: Montgomery products of any odd p < 2^32", "spmv.hip",
