@@ -48,6 +48,7 @@ constexpr int BS_PASSROWS = 32;
 // an empty slot of the pass table points at a spare row of the ring (row BS_RING, i.e. word offset RING * RSTR: bs_pass_empty)
 // with coefficient 0: the signed kernels run every lane through the same reads, multiply-adds and write, without a branch
 constexpr uint32_t BS_NONE = 0xFFFFFFFFu;
+constexpr int BS_XCDS = 8;         // XCDs of an MI355X in its default partition (backsolve_kernel: which slabs share an L2; any value gives the same R)
 
 template <typename T> T *dalloc(int64_t count)
 {
@@ -77,7 +78,8 @@ struct BsArgs {
 	int plain;                    // coefficients (y) are plain residues (p < 2^16), not Montgomery form
 	int sparse_init;              // 1: the kernel scatters U_n itself (few entries); 0: R was pre-filled by bs_init_kernel
 	int r;
-	unsigned long long *prof;     // SPASM_HIP_BS_PROFILE=1: 8 counters, shader-clock cycles of workgroup 0 per stage of a chunk, summed over the chunks
+	int Sm;                       // columns of R
+	unsigned long long *prof;    // SPASM_HIP_BS_PROFILE=1: 8 counters, shader-clock cycles of workgroup 0 per stage of a chunk, summed over the chunks
 	int sgn;                      // signed 16-bit entries (the SGN kernels); coefficients are negated balanced residues
 	MontDev F;
 	SgnDev G;
@@ -217,22 +219,57 @@ template <int HI> __device__ __forceinline__ uint32_t bs_ring_at(uint32_t packed
 }
 using bs_lds_word = __attribute__((address_space(3))) uint32_t;
 
-// LPR lanes (words) per row of a slab: a row of a slab is LPR * 4 bytes (128 B with LPR = 32: whole cache lines, half
+// WPL consecutive words of a row of R, as a lane moves them in phases A and C: one access of WPL * 4 bytes (WPL = 4: 16-byte
+// aligned, the caller sees to it).  `present` false: nothing is read, the words are 0.
+template <int WPL> __device__ __forceinline__ void bs_load_words(bool present, const uint32_t *at, uint32_t (&w)[WPL])
+{
+	static_assert(WPL == 1 || WPL == 4, "a lane moves one word or four");
+	if constexpr (WPL == 4) {
+		const uint4 t = present ? *reinterpret_cast<const uint4 *>(at) : uint4{0u, 0u, 0u, 0u};
+		w[0] = t.x, w[1] = t.y, w[2] = t.z, w[3] = t.w;
+	} else {
+		w[0] = present ? *at : 0u;
+	}
+}
+template <int WPL> __device__ __forceinline__ void bs_store_words(uint32_t *at, const uint32_t (&w)[WPL])
+{
+	if constexpr (WPL == 4)
+		*reinterpret_cast<uint4 *>(at) = uint4{w[0], w[1], w[2], w[3]};
+	else
+		*at = w[0];
+}
+
+// the largest number of rows <= `rows` for which `nw` waves of that many rows divide `ring`
+constexpr int bs_rows_dividing(int rows, int nw, int ring)
+{
+	return (rows <= 1 || ring % (rows * nw) == 0) ? rows : bs_rows_dividing(rows - 1, nw, ring);
+}
+
+// LPR words per row of a slab: a row of a slab is LPR * 4 bytes (128 B with LPR = 32: whole cache lines, half
 // as many requests as 64-byte segments -- the kernel is bound by the rate of such requests).
-// NW waves per workgroup; a wave instruction covers 64 / LPR rows.
+// NW waves per workgroup.  In phases A and C a lane holds WPL consecutive words of a row, a row is QPR = LPR / WPL lanes and a
+// wave instruction covers RS rows.  WPL = 4 where every wave has one word of a row in phase B and the row is whole quads
+// (slabs of 12 and 8 words): whatever is done per row and not per word -- the head, its selects, the addresses, the guard --
+// is then paid once per four words, and memory is reached 16 bytes at a time.  Elsewhere a lane holds one word.
 // RING / PASSROWS / PASSCAP: rows per chunk, rows per phase-B pass, passes per chunk -- the plan (backsolve_plan) is built
 // for the values of the kernel that will run it, and for its RSTR (BsImage::ring, passrows, passcap, rstr).
 template <bool PACKED, int LPR, int NW, int RING = BS_RING, int PASSROWS = BS_PASSROWS, int PASSCAP = BS_PASSCAP> struct BsGeom {
 	static constexpr int RING_ = RING, PASSROWS_ = PASSROWS, PASSCAP_ = PASSCAP;
 	static constexpr int THREADS = 64 * NW;
-	static constexpr int RS = 64 / LPR;
+	static constexpr int WPL = (NW == LPR && LPR % 4 == 0) ? 4 : 1;
+	static constexpr int QPR = LPR / WPL;
+	// rows per wave instruction: as many as the wave has lanes for; WPL = 4: the largest such number for which an iteration
+	// of the workgroup divides the chunk (12 words: 20 rows on 60 lanes, 240 per iteration, 5 iterations; 8 words: 32, 256, 3)
+	static constexpr int RS = (WPL == 1) ? 64 / QPR : bs_rows_dividing(64 / QPR, NW, RING);
+	static constexpr int RS1 = 64 / LPR;                   // the same with one word per lane (the long lists of outside dependencies)
 	static constexpr int CW = LPR * Word<PACKED>::CPL;     // columns per slab
 	static constexpr int ROWS_PER_ITER = RS * NW;
 	static constexpr int ITERS = RING / ROWS_PER_ITER;
 	// rows in flight per lane in phase A.  Eight waves (two per SIMD: 256 registers each) take a whole chunk in ONE pass --
 	// a pass is a round trip to memory, and a chunk has little else to hide it behind
 	static constexpr int UNR = (NW >= 8 && ITERS <= 24) ? ITERS : (ITERS % 12 == 0) ? 12 : 8;
-	static constexpr int LANES_USED = RS * LPR;            // (LPR need not divide 64: the lanes beyond RS whole rows idle in phases A and C)
+	static constexpr int LANES_USED = RS * QPR;            // (the lanes beyond RS whole rows idle in phases A and C)
+	static_assert(LPR % WPL == 0 && LANES_USED <= 64, "a row is whole lanes, a wave instruction whole rows");
 	static_assert(RING % ROWS_PER_ITER == 0 && ITERS % UNR == 0, "phase A is unrolled in passes of UNR rows");
 	static constexpr int N_NEAR = (BS_NEARCAP + THREADS - 1) / THREADS;      // metadata words a thread carries for the next chunk
 	static constexpr int N_ROW = (RING + THREADS - 1) / THREADS;
@@ -248,6 +285,16 @@ template <bool PACKED, bool PLAIN, int LPR, int NW, bool SGN = false, int RING =
 __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b)
 {
 	static_assert(!SGN || (PACKED && PLAIN), "signed entries are packed 16-bit entries");
+	// For speed only (any one-to-one assignment of slabs to workgroups computes the same R: a workgroup reads nothing but what it
+	// wrote itself).  Every XCD has an L2 of its own, and workgroups have been observed to go to the XCDs in turn (workgroup i
+	// to XCD i mod 8; the hardware does not promise it).  A slab row is a fraction of a 128-byte line: with slab = workgroup,
+	// the slabs that share a line sit on different XCDs, each L2 pulls the line in for phase A and writes its part of it back
+	// after phase C.  So workgroups i, i + 8, i + 16, ... take a RUN of neighbouring slabs: on such a chip a line of R is read
+	// into, and written from, one L2 (but for the lines where two runs meet).  The grid is BS_XCDS whole runs.
+	const int nslabs = (b.Sm + LPR * Word<PACKED>::CPL - 1) / (LPR * Word<PACKED>::CPL);
+	const int slab = (int) (blockIdx.x % BS_XCDS) * (int) (gridDim.x / BS_XCDS) + (int) (blockIdx.x / BS_XCDS);
+	if (slab >= nslabs)
+		return;
 	const uint32_t bm = PLAIN ? (uint32_t) (0x100000000ull / b.F.p) : 0u;
 	const SgnDev G = b.G;
 	using Geo = BsGeom<PACKED, LPR, NW, RING, PASSROWS, PASSCAP>;
@@ -265,7 +312,8 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 	// from wave to wave; the one place where global stores must be visible to other waves (after phase C) keeps
 	// __syncthreads().
 	auto lds_barrier = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-	const int rs = lane / LPR, wl = lane % LPR;           // row slot of the lane, its word inside the row (phases A and C)
+	constexpr int WPL = Geo::WPL;
+	const int rs = lane / Geo::QPR, wl = lane % Geo::QPR * WPL;          // row slot of the lane, its first word inside the row (phases A and C)
 	constexpr int RSTR = Geo::RSTR;                        // words between two rows of the ring
 	constexpr uint32_t SPARE = (uint32_t) (RING * RSTR);   // the spare row (row RING), where the empty slots of the pass table point
 	// phase B splits the COLUMNS among the waves: a wave owns WPW words of every row, a wave instruction covers RSB rows
@@ -274,7 +322,7 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 	static_assert(PASSROWS % RSB == 0, "a pass is a whole number of wave instructions");
 	const MontDev F = b.F;
 	const int64_t ldw = b.ldR / Word<PACKED>::CPL;       // row stride of R in words
-	uint32_t *Rs = static_cast<uint32_t *>(b.R) + (int64_t) blockIdx.x * LPR + wl;
+	uint32_t *Rs = static_cast<uint32_t *>(b.R) + (int64_t) slab * LPR + wl;
 	// a row of R starts at row * ldw words; ldw is a multiple of 256 (rows are padded to 512 columns), and row * (ldw / 256)
 	// fits 32 bits for any R below 4 TB.  The plan hands every dependency over as that product (its OFFSET, in units of 256
 	// words): an address is a shift and an add.  The chunk's own rows are the offset of its first row (one scalar multiply
@@ -284,10 +332,12 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 	const int slot0 = wave * Geo::RS + rs;          // this lane's row slot within an iteration
 	const uint32_t slot0_off = (uint32_t) slot0 * ldw256;
 	const uint32_t iter_off = (uint32_t) Geo::ROWS_PER_ITER * ldw256;          // (uniform)
-	// lanes that hold a word of a row in phases A and C: all of them when LPR divides 64; and the word must exist (the last
-	// slab of a row may reach beyond the padded row when LPR does not divide its length)
-	const bool lane_ok = lane < Geo::LANES_USED && (int64_t) blockIdx.x * LPR + wl < ldw;
-	const int col_lo = blockIdx.x * Geo::CW;        // columns [col_lo, col_lo + CW) belong to this workgroup
+	// lanes that hold words of a row in phases A and C: all of them when the rows of a wave instruction fill it; and the words
+	// must exist (the last slab of a row may reach beyond the padded row when LPR does not divide its length; the length and
+	// the start of a slab are multiples of WPL, so the lane's words are all inside or all outside)
+	static_assert(WPL == 1 || (LPR % WPL == 0 && 256 % WPL == 0), "WPL words at a multiple of WPL: one aligned access, inside the padded row or outside it");
+	const bool lane_ok = lane < Geo::LANES_USED && (int64_t) slab * LPR + wl < ldw;
+	const int col_lo = slab * Geo::CW;        // columns [col_lo, col_lo + CW) belong to this workgroup
 
 	// metadata of a chunk (the same for every slab: served by the L2) travels through registers: the loads for chunk
 	// k + 1 are issued when chunk k starts and land in LDS when it is done
@@ -378,7 +428,7 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 	// stage timer (SPASM_HIP_BS_PROFILE): thread 0 of workgroup 0 reads the shader clock at every stage boundary
 	unsigned long long pt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 	unsigned long long t_last = 0;
-	const bool profiling = b.prof != nullptr && blockIdx.x == 0 && tid == 0;
+	const bool profiling = b.prof != nullptr && slab == 0 && tid == 0;
 	auto tick = [&](int q) {
 		if (profiling) {
 			const unsigned long long now = __builtin_readcyclecounter();
@@ -408,7 +458,7 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 			fetch_chunk(k + 2);
 		tick(0);          // descriptor + issue of the next chunk's metadata
 
-		// ---- phase A: own row + dependencies outside the chunk, up to 3 * UNR loads in flight per lane ----
+		// ---- phase A: own row + dependencies outside the chunk, up to 3 * UNR loads (of WPL words) in flight per lane ----
 		// SPARSE (sparse_init): the rows start at zero IN REGISTERS -- R is not read for them, the ring is neither zeroed nor read --
 		// and the few entries of U_n are added to the ring afterwards.  Otherwise a row starts as what bs_init_kernel put into R.
 		const uint32_t lo_off = (uint32_t) ch.lo * ldw256;          // (uniform: a scalar multiply)
@@ -421,7 +471,7 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 				// once).  The pre-filled path has the row's own word in flight as well: no registers for them, it reads them again;
 				// so do 32-bit coefficients in the workgroups of sixteen waves.
 				constexpr bool KEEP = SPARSE && (PLAIN || NW < 16);          // (sixteen waves have 128 registers each)
-				uint32_t acc[SPARSE ? 1 : Geo::UNR], v0[Geo::UNR], v1[Geo::UNR], c0[KEEP ? Geo::UNR : 1], c1[(KEEP && !PLAIN) ? Geo::UNR : 1];
+				uint32_t acc[SPARSE ? 1 : Geo::UNR][WPL], v0[Geo::UNR][WPL], v1[Geo::UNR][WPL], c0[KEEP ? Geo::UNR : 1], c1[(KEEP && !PLAIN) ? Geo::UNR : 1];
 				// offset of the lane's own row, stepped from iteration to iteration (hidden from the compiler's algebra, which
 				// would turn the sum back into (first row + slot) * stride: a quarter-rate multiply per access)
 				uint32_t own_off = lo_off + (uint32_t) (pass * Geo::UNR) * iter_off + slot0_off;
@@ -438,24 +488,23 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 							c1[u] = h.w;
 					}
 					if constexpr (!SPARSE) {
-						acc[u] = ok ? *at_off(own_off) : 0u;
+						bs_load_words<WPL>(ok, at_off(own_off), acc[u]);
 						own_off += iter_off;
 					}
 					if constexpr (LPR <= 16 && 64 % LPR == 0) {
 						// no branch around the loads: an absent dependency reads the chunk's own first row -- a valid address -- and
 						// is multiplied by the coefficient 0 of its slot, or skipped, below (64-byte rows: 2.84 -> 2.75 ms on mk13.b5,
 						// 9.2 -> 6.1 ms with 32-bit entries; with 128-byte rows the wasted lines cost more than the branches)
-						v0[u] = *at_off((ok && a0 != BS_NONE) ? a0 : lo_off);
-						v1[u] = *at_off((ok && a1 != BS_NONE) ? a1 : lo_off);
+						bs_load_words<WPL>(true, at_off((ok && a0 != BS_NONE) ? a0 : lo_off), v0[u]);
+						bs_load_words<WPL>(true, at_off((ok && a1 != BS_NONE) ? a1 : lo_off), v1[u]);
 					} else {
-						v0[u] = (ok && a0 != BS_NONE) ? *at_off(a0) : 0u;
-						v1[u] = (ok && a1 != BS_NONE) ? *at_off(a1) : 0u;
+						bs_load_words<WPL>(ok && a0 != BS_NONE, at_off(a0), v0[u]);
+						bs_load_words<WPL>(ok && a1 != BS_NONE, at_off(a1), v1[u]);
 					}
 				}
 #pragma unroll
 				for (int u = 0; u < Geo::UNR; u++) {
 					const int s = (pass * Geo::UNR + u) * Geo::ROWS_PER_ITER + slot0;          // (< RING: a head that exists, whatever it holds)
-					uint32_t x = SPARSE ? 0u : acc[u];
 					uint32_t k0, k1;          // coefficients: both in k0 when PLAIN
 					if constexpr (KEEP) {
 						k0 = c0[u];
@@ -468,30 +517,37 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 						k0 = h.y;
 						k1 = h.w;
 					}
-					if constexpr (SGN) {
-						// no flags: an absent dependency has the coefficient 0 (and was loaded as 0, or as a row that exists), and a row
-						// without dependencies comes out of the reduction as it went in (|x| <= p/2: the nearest multiple of p is 0)
-						int lo, hi;
-						if constexpr (SPARSE) {
-							sgn_mad_half<0, true>(v0[u], k0, lo, hi);
+					uint32_t x[WPL];
+#pragma unroll
+					for (int j = 0; j < WPL; j++) {
+						x[j] = SPARSE ? 0u : acc[u][j];
+						if constexpr (SGN) {
+							// no flags: an absent dependency has the coefficient 0 (and was loaded as 0, or as a row that exists), and a row
+							// without dependencies comes out of the reduction as it went in (|x| <= p/2: the nearest multiple of p is 0)
+							int lo, hi;
+							if constexpr (SPARSE) {
+								sgn_mad_half<0, true>(v0[u][j], k0, lo, hi);
+							} else {
+								sgn_unpack(x[j], lo, hi);
+								sgn_mad_half<0, false>(v0[u][j], k0, lo, hi);
+							}
+							sgn_mad_half<1, false>(v1[u][j], k0, lo, hi);
+							x[j] = sgn_pack(sgn_reduce(lo, G), sgn_reduce(hi, G));
 						} else {
-							sgn_unpack(x, lo, hi);
-							sgn_mad_half<0, false>(v0[u], k0, lo, hi);
+							// (no kernel without signed entries has WPL = 4 today: this form is compiled with one word per lane only)
+							const uint32_t q0 = PLAIN ? (k0 & 0xFFFFu) : k0, q1 = PLAIN ? (k0 >> 16) : k1;
+							if (q0 != 0u)
+								x[j] = w_submul<PACKED, PLAIN>(x[j], v0[u][j], q0, F, bm);
+							if (q1 != 0u)
+								x[j] = w_submul<PACKED, PLAIN>(x[j], v1[u][j], q1, F, bm);
 						}
-						sgn_mad_half<1, false>(v1[u], k0, lo, hi);
-						x = sgn_pack(sgn_reduce(lo, G), sgn_reduce(hi, G));
-					} else {
-						if constexpr (PLAIN) {
-							k1 = k0 >> 16;
-							k0 &= 0xFFFFu;
-						}
-						if (k0 != 0u)
-							x = w_submul<PACKED, PLAIN>(x, v0[u], k0, F, bm);
-						if (k1 != 0u)
-							x = w_submul<PACKED, PLAIN>(x, v1[u], k1, F, bm);
 					}
-					if (s < nrows && lane_ok)
-						ring[s * RSTR + wl] = x;
+					// (the ring's rows are an odd number of words apart: WPL = 4 goes in as two pairs of words, not as 16 aligned bytes)
+					if (s < nrows && lane_ok) {
+#pragma unroll
+						for (int j = 0; j < WPL; j++)
+							ring[s * RSTR + wl + j] = x[j];
+					}
 				}
 			}
 		};
@@ -530,12 +586,26 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 		tick(2);          // non-pivotal entries of U added to the rows
 		if (ch.npn < 0) {          // (bit 31 of the descriptor)
 			// rows with more than two outside dependencies (long rows of U): the rest of their lists
-			for (int s = slot0; s < nrows; s += Geo::ROWS_PER_ITER) {
+			// (few rows have them: this stage keeps ONE word of a row per lane, RS1 rows per wave instruction.  WPL = 4: its
+			//  mapping is worked out here, as phase B's is, instead of living in registers through phase A)
+			int slot1 = slot0, wl1 = wl;
+			bool ok1 = lane_ok;
+			const uint32_t *R1 = Rs;
+			if constexpr (WPL > 1) {
+				int tid_l = tid;
+				asm volatile("" : "+v"(tid_l));
+				wl1 = (tid_l & 63) % LPR;
+				slot1 = (tid_l >> 6) * Geo::RS1 + (tid_l & 63) / LPR;
+				ok1 = (tid_l & 63) < Geo::RS1 * LPR && (int64_t) slab * LPR + wl1 < ldw;
+				R1 = static_cast<const uint32_t *>(b.R) + (int64_t) slab * LPR + wl1;
+			}
+			auto at_off1 = [&](uint32_t off) -> const uint32_t * { return R1 + ((uint64_t) off << 8); };
+			for (int s = slot1; s < nrows; s += Geo::RS1 * NW) {
 				const int c = ch.lo + s;
 				const uint64_t e0 = b.far_rp[c], e1 = b.far_rp[c + 1];
-				if (e0 == e1 || !lane_ok)
+				if (e0 == e1 || !ok1)
 					continue;
-				uint32_t x = ring[s * RSTR + wl];
+				uint32_t x = ring[s * RSTR + wl1];
 				if constexpr (SGN) {
 					int lo, hi;
 					sgn_unpack(x, lo, hi);
@@ -543,7 +613,7 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 #pragma unroll
 						for (int t = 0; t < 4; t++) {
 							const uint2 en = (e + t < e1) ? b.far[e + t] : uint2{0u, 0u};
-							sgn_mad((e + t < e1) ? *at_off(en.x) : 0u, (int) en.y, lo, hi);          // (en.x: the row's offset)
+							sgn_mad((e + t < e1) ? *at_off1(en.x) : 0u, (int) en.y, lo, hi);          // (en.x: the row's offset)
 						}
 						lo = sgn_reduce(lo, G);
 						hi = sgn_reduce(hi, G);
@@ -552,10 +622,10 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 				} else {
 					for (uint64_t e = e0; e < e1; e++) {
 						const uint2 en = b.far[e];
-						x = w_submul<PACKED, PLAIN>(x, *at_off(en.x), en.y, F, bm);
+						x = w_submul<PACKED, PLAIN>(x, *at_off1(en.x), en.y, F, bm);
 					}
 				}
-				ring[s * RSTR + wl] = x;
+				ring[s * RSTR + wl1] = x;
 			}
 			lds_barrier();
 		}
@@ -672,15 +742,22 @@ __global__ __launch_bounds__(64 * NW, WGS_PER_CU) void backsolve_kernel(BsArgs b
 			uint32_t off = lo_off + slot0_off;
 			asm volatile("" : "+v"(off));          // (as in phase A: stepped, not multiplied)
 			for (int s = slot0; s < nrows; s += Geo::ROWS_PER_ITER, off += iter_off)
-				if (lane_ok)
-					*at_off(off) = ring[s * RSTR + wl];
+				if (lane_ok) {
+					uint32_t x[WPL];
+#pragma unroll
+					for (int j = 0; j < WPL; j++)
+						x[j] = ring[s * RSTR + wl + j];
+					bs_store_words<WPL>(at_off(off), x);
+				}
 		}
-		__syncthreads();          // (workgroup-scope release/acquire: later chunks read these rows; LDS metadata is free)
-		tick(5);          // phase C
+		tick(5);          // phase C: the ring read and the stores issued
+		// the metadata of the next chunk goes into LDS behind the stores: its targets (fh, ptab, near) were last read in phase B,
+		// which the barrier above has ended, and phase C reads the ring alone.  ONE barrier then ends both
 		if (k + 1 < b.nchunks)
 			store_meta();
-		__syncthreads();
-		tick(6);          // metadata of the next chunk into LDS
+		__syncthreads();          // (workgroup-scope release/acquire: later chunks read these rows; the metadata is in place)
+		tick(6);          // metadata of the next chunk into LDS + the barrier (which waits for LDS traffic only: the compiler puts no
+		                  // vmcnt(0) in front of a workgroup-scope barrier here, the waves of a workgroup share the CU's L1)
 	}
 	if (profiling)
 		for (int q = 0; q < 8; q++)
@@ -1874,8 +1951,9 @@ void launch_backsolve_variant(const BsArgs &b, int Sm, hipStream_t stream, const
 		                              hipFuncAttributeMaxDynamicSharedMemorySize, (int) G::LDS_BYTES));
 		configured = true;
 	}
-	hipLaunchKernelGGL((backsolve_kernel<PACKED, PLAIN, LPR, NW, SGN, RING, PASSROWS, PASSCAP, WGS_PER_CU>), dim3((unsigned) ((Sm + G::CW - 1) / G::CW)),
-	                   dim3(64 * NW), G::LDS_BYTES, stream, b);
+	const int nslabs = (Sm + G::CW - 1) / G::CW;
+	hipLaunchKernelGGL((backsolve_kernel<PACKED, PLAIN, LPR, NW, SGN, RING, PASSROWS, PASSCAP, WGS_PER_CU>),
+	                   dim3((unsigned) ((nslabs + BS_XCDS - 1) / BS_XCDS * BS_XCDS)), dim3(64 * NW), G::LDS_BYTES, stream, b);
 }
 
 template <bool PACKED, bool PLAIN> void launch_apply_variant(const ApplyArgs &d, int blocks, size_t lds, hipStream_t stream)
@@ -2403,6 +2481,7 @@ void backsolve_build(const spasm_hip_dfact *F, hipStream_t stream)
 	b.np = B.d_np;
 	b.np_row = B.d_np_row;
 	b.r = B.r;
+	b.Sm = B.Sm;
 	b.plain = B.plain ? 1 : 0;
 	b.sgn = B.sgn ? 1 : 0;
 	b.G = sgn_setup(F->prime);
@@ -2480,8 +2559,8 @@ void backsolve_build(const spasm_hip_dfact *F, hipStream_t stream)
 		unsigned long long h[8];
 		HIP_CHECK(hipMemcpyAsync(h, b.prof, sizeof(h), hipMemcpyDeviceToHost, stream));
 		HIP_CHECK(hipStreamSynchronize(stream));
-		static const char *const stage[7] = {"descriptor + metadata issue", "phase A", "non-pivotal entries added", "long outside lists", "phase B", "phase C",
-		                                     "metadata into LDS"};
+		static const char *const stage[7] = {"descriptor + metadata issue", "phase A", "non-pivotal entries added", "long outside lists", "phase B", "phase C (issue)",
+		                                     "metadata into LDS + barrier"};
 		unsigned long long tot = 0;
 		for (int q = 0; q < 7; q++)
 			tot += h[q];
